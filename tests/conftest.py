@@ -7,6 +7,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+# torch before any test loads libplba_hip.so, as in __graft_entry__.build(): torch's wheel carries its own HIP / HSA runtime, and a
+# process that loads the system ROCm's through libplba_hip.so first ends up with two HSA runtimes, the second of which finds no device.
+# A whole-suite run on a GPU machine did: the CPU tests (test_abi_cpu.py first) dlopen the library, then every GPU test failed.
+try:
+    import torch  # noqa: F401,E402
+except ImportError:
+    pass
+
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")

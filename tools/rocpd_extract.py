@@ -100,7 +100,7 @@ def pmc(db_fetch, db_write, out, bench_json=None, command=None, db_req=None):
         except (OSError, ValueError, KeyError, IndexError):
             pass
     json.dump({"note": "per-launch averages; traffic = fetched bytes from the L2's read-request counters by size (round 5) + WRITE_SIZE — or (2 x FETCH_SIZE + WRITE_SIZE) KB, the gfx950 correction of MI355X_MICROARCH.md, where no request-size pass was made; "
-                       "command: " + (command or "rocprofv3 --pmc <counter> -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-config5-leg") + " (one pass per counter)",
+                       "command: " + (command or "rocprofv3 --pmc <counter> -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-config5-leg") + " (one pass per counter)",
                "csrc_sha16": h.hexdigest()[:16],      # bench.py quotes these numbers only for the kernel sources they were measured on
                "kernels": res}, open(out, "w"), indent=1, sort_keys=True)
 
