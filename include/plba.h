@@ -222,7 +222,8 @@ int plba_get_levels(plba_problem* p, plba_edge_kind kind, uint8_t* level);
  *     Landmark indices of the added observations are those BEFORE the slide for landmarks that stay (they must stay) and
  *     Np_before + i / Nl_before + i for the i-th added one; both lists sorted by that index.  A kept landmark's new
  *     observations are listed after its old ones, as the reference's kf_obs_list grows.
- *   - all edges are level 0 again and the prior is kept as set: call plba_set_prior for the new window's prior (or clear it).
+ *   - all edges are level 0 again and the prior is kept as set: call plba_set_prior for the new window's prior (or clear it), or
+ *     let plba_marginalize_to_prior have made it before the slide.
  * point_map[Np_before] / line_map[Nl_before] (optional) receive each old landmark's new index or -1.  The structure the next
  * plba_optimize builds — and therefore every result, bit for bit — is that of a fresh handle given the same window through
  * plba_set_* (tests/test_slide_window.py).  One GPU only (a sharded problem takes a fresh upload). */
@@ -299,6 +300,34 @@ int  plba_marginalize_factors(plba_problem* p, int n_imu, const int32_t* imu_edg
                               int n_ln, const int32_t* line_edges, int use_prior, int n_drop, const int32_t* drop_vid,
                               plba_prior* out);
 void plba_prior_free(plba_prior* pr);
+/* The marginalization of plba_marginalize (same factor selection, same result), whose result REPLACES this problem's prior on the
+ * device instead of coming back to the host: the reference's MapHandler::marg_info, built at the end of one BA call and first read
+ * at the start of the next (src/mapHandler.cpp:6190-6197 -> 6007-6034), without its PCIe round trip.  Returns once the work is
+ * enqueued.  out3 (may be NULL) = [n, m, nv].
+ *  1. The old prior is used as a factor exactly as in plba_marginalize; the new prior replaces it in stream order.
+ *  2. vid, size, idx, n, m and nv are computed on the host: they are the problem's prior metadata when the call returns.
+ *  3. x0, J0, r0, A' and b' stay on the device: they reach the host only when plba_get_prior asks for them.
+ *  4. Both  plba_optimize -> plba_marginalize_to_prior -> plba_slide_window -> plba_optimize  (the reference's life-cycle) and
+ *     plba_marginalize_to_prior -> plba_optimize  on the same window work: unlike plba_set_prior, this call does not make
+ *     plba_slide_window refuse.  The next plba_optimize reads the new prior as if plba_set_prior had been given it.
+ *  5. The marginalization is resolved by the first later call that consumes the prior: plba_optimize, plba_get_prior,
+ *     plba_marginalize*, plba_debug_get("marg_path") (refused after a slide until the next plba_optimize, as before).  A call that
+ *     rebuilds a slid window before that — plba_get_keyframes / _points / _lines, plba_gate_outliers, plba_cull_observations and the
+ *     other calls that build the window when they find it changed — builds it with the new prior and so resolves it too.
+ *  6. Errors that only the device can find (the Jacobi sweep limit, a failed dense fallback) surface at that resolution, with the
+ *     status and text plba_marginalize gives them.  After any error of this call or of its resolution (argument checks before the
+ *     marginalization starts aside) the problem holds no prior.
+ *  7. plba_set_prior and plba_destroy wait for a pending marginalization, release its buffers and drop its result.
+ *  8. The call blocks the calling thread only (a) on the dense path chosen on the host (options.marg_exact = 2), (b) when the kept
+ *     block exceeds the in-LDS limit (n > 140): both run the HBM Jacobi, which reads its convergence back once per sweep, and the
+ *     latter decides the certificate on the host; (c) when options.diag asks for the marginalization dump.  With the default
+ *     marg_exact = 1 the certificate is decided on the device, and a failed certificate moves the dense work — and its waits — into
+ *     the resolving call.  plba_debug_get("host_waits") counts the library's blocking waits on the device.
+ *  9. A sharded problem (plba_set_shard, world > 1) is refused with PLBA_ERR_STATE, as plba_slide_window refuses it. */
+int  plba_marginalize_to_prior(plba_problem* p, int first_kf, int max_edges_per_kind, int32_t* out3);
+/* The problem's current prior, as plba_marginalize would have returned it (free with plba_prior_free).  m, Ar and br are filled
+ * only for a prior made by plba_marginalize_to_prior (else 0 / NULL).  No prior: PLBA_ERR_STATE. */
+int  plba_get_prior(plba_problem* p, plba_prior* out);
 /* MarginalizationInfo::eps (IMU/marginalization.h:99 — a public, mutable member; the thresholds of
  * IMU/marginalization.cpp:353,365-366 read it): replaces options.marg_eps for the following plba_marginalize* calls. */
 int  plba_set_marg_eps(plba_problem* p, double eps);
@@ -368,7 +397,8 @@ int plba_lba_visual(plba_problem* p, const plba_lba_options* opt, int K, const d
  * "bp" (P), "x" (P + 3Np + 6Nl after a solve), "hll_pt" (Np*9), "bl_pt" (Np*3), "hll_ln" (Nl*36),
  * "bl_ln" (Nl*6), "err_pvr" (M*9), "err_bias" (M*6), "err_prior" (n), "pose_dim" (1), "chi2" (1),
  * "maxdiag" (1); "marg_path" (5, after plba_marginalize*): [0] 0 = block-wise pseudo-inverse taken, 1 = dense
- * eigen-decomposition of Amm; [1..4] the certificate's w_max, smallest kept landmark eigenvalue, tau, smallest pivot. */
+ * eigen-decomposition of Amm; [1..4] the certificate's w_max, smallest kept landmark eigenvalue, tau, smallest pivot;
+ * "host_waits" (1, at any time, waits for nothing): how often the library has blocked the calling thread on the device. */
 int plba_debug_build(plba_problem* p, double lambda, int do_solve);
 int plba_debug_get(plba_problem* p, const char* what, double* out, size_t cap, size_t* n);
 /* the same entry under its round-1 name (tests/test_gpu_parity.py); product code calls plba_dense_solve */

@@ -75,7 +75,7 @@ _P = C.c_void_p  # plba_problem*
 
 # entry points of the product that have no counterpart in the reference's algorithm (memory management of the device-resident window): the
 # CPU oracle — a restatement of the reference — does not implement them
-PRODUCT_ONLY = {"slide_window", "get_sizes"}
+PRODUCT_ONLY = {"slide_window", "get_sizes", "marginalize_to_prior", "get_prior"}
 
 # name -> (restype, argtypes); every symbol plba.h declares
 SIGNATURES = {
@@ -114,6 +114,8 @@ SIGNATURES = {
     "marginalize": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(Prior)]),
     "marginalize_factors": (C.c_int, [_P, C.c_int, c_int32_p, C.c_int, c_int32_p, C.c_int, c_int32_p, C.c_int, C.c_int, c_int32_p, C.POINTER(Prior)]),
     "preintegrate": (C.c_int, [_P, C.c_int, c_int32_p, C.POINTER(C.c_longdouble), c_double_p, c_double_p, C.POINTER(C.c_longdouble), C.POINTER(C.c_longdouble), c_double_p, c_double_p, C.c_double, C.c_double, c_double_p]),
+    "marginalize_to_prior": (C.c_int, [_P, C.c_int, C.c_int, c_int32_p]),
+    "get_prior": (C.c_int, [_P, C.POINTER(Prior)]),
     "prior_free": (None, [C.POINTER(Prior)]),
     "set_marg_eps": (C.c_int, [_P, C.c_double]),
     "lba_default_options": (None, [C.POINTER(LbaOptions)]),
@@ -396,6 +398,23 @@ class Problem:
     def marginalize(self, first_kf=0, max_edges=50):
         pr = Prior()
         self.call("marginalize", int(first_kf), int(max_edges), C.byref(pr))
+        return self._prior_dict(pr)
+
+    def marginalize_to_prior(self, first_kf=0, max_edges=50):
+        """plba_marginalize_to_prior: the marginalization's result becomes this problem's prior on the device (nothing comes back);
+        returns dict(n, m, nv)."""
+        out3 = np.zeros(3, np.int32)
+        self.call("marginalize_to_prior", int(first_kf), int(max_edges), _ip(out3))
+        self.dims["n_prior"] = int(out3[0])
+        return dict(n=int(out3[0]), m=int(out3[1]), nv=int(out3[2]))
+
+    def get_prior(self):
+        """plba_get_prior: the current prior, as marginalize() returns it."""
+        pr = Prior()
+        self.call("get_prior", C.byref(pr))
+        return self._prior_dict(pr)
+
+    def _prior_dict(self, pr):
         n, nv = pr.n, pr.nv
 
         def arr(p, cnt, dt):
@@ -406,7 +425,7 @@ class Problem:
                    x0=arr(pr.x0, nx, np.float64),
                    J0=arr(pr.J0, n * n, np.float64).reshape(n, n).T.copy(),  # colmajor -> J0[r, c]
                    r0=arr(pr.r0, n, np.float64),
-                   Ar=arr(pr.Ar, n * n, np.float64).reshape(n, n), br=arr(pr.br, n, np.float64))
+                   Ar=arr(pr.Ar, n * n, np.float64).reshape(n, n) if pr.Ar else None, br=arr(pr.br, n, np.float64) if pr.br else None)
         self.lib.fn["prior_free"](C.byref(pr))
         return out
 

@@ -42,6 +42,7 @@ static const size_t PARK_MAX = 2;
 // every field a caller can see or set goes back to what a new plba_problem() has; device buffers, the batch blocks, the events and the
 // structure cache stay
 static void reset_for_reuse(plba_problem* p, const plba_options* opt) {
+    marg_discard(p);      // (plba_destroy has done so already)
     if (opt) p->opt = *opt; else plba_default_options(&p->opt);
     p->err[0] = 0;
     p->stream = p->ctx.stream; p->own_stream = true;
@@ -55,6 +56,7 @@ static void reset_for_reuse(plba_problem* p, const plba_options* opt) {
     p->po_pt.clear(); p->po_kf.clear(); p->lo_ln.clear(); p->lo_kf.clear(); p->po_uv.clear(); p->po_w.clear(); p->lo_l.clear(); p->lo_w.clear();
     p->level.clear(); p->imu_i.clear(); p->imu_j.clear(); p->imu_pre.clear(); p->imu_ipvr.clear(); p->imu_ibias.clear();
     p->pr_n = p->pr_nv = 0; p->pr_vid.clear(); p->pr_size.clear(); p->pr_idx.clear(); p->pr_x0.clear(); p->pr_J0.clear(); p->pr_r0.clear();
+    p->prior_dev = false; p->prior_changed = false; p->pr_m = 0; p->host_waits = 0;
     memset(&p->rob, 0, sizeof p->rob);
     p->rank = 0; p->world = 1; p->xfn = nullptr; p->xuser = nullptr;
     p->dirty = true; p->P = p->Ppad = p->ld = p->L = p->E = 0; p->cur = 0;
@@ -194,6 +196,7 @@ int plba_create(const plba_options* opt, plba_problem** out) {
 void plba_destroy(plba_problem* p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
+    marg_discard(p);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     if (p->have_ctx) {
         (void)hipStreamSynchronize(p->ctx.stream);
@@ -337,7 +340,9 @@ int plba_set_imu_edges(plba_problem* p, int M, const int32_t* ki, const int32_t*
 int plba_set_prior(plba_problem* p, int n, int nv, const int32_t* vid, const int32_t* size, const int32_t* idx, const double* x0,
                    const double* J0, const double* r0) {
     if (!p) return PLBA_ERR_INVALID;
+    marg_discard(p);      // a pending plba_marginalize_to_prior: waited for, its result dropped
     p->dirty = true;
+    p->prior_dev = false; p->prior_changed = false; p->pr_m = 0;
     if (nv == 0) { p->pr_n = 0; p->pr_nv = 0; return PLBA_OK; }
     if (n <= 0 || nv < 0 || !vid || !size || !idx || !x0 || !J0 || !r0) return PLBA_ERR_INVALID;
     int tot = 0, nx = 0;
@@ -399,7 +404,7 @@ int plba_dense_solve(plba_problem* p, int n, const double* A, const double* b, d
     if (Ppad / 32 <= NINV_MAX_T) { HIPCK(p, Ninv.alloc((size_t)2 * Ppad * ld)); d.Ninv = Ninv.p; d.Nwork = Ninv.p + (size_t)Ppad * ld; }
     launch_cholesky(d, p->opt.use_mfma != 0, 1, p->stream);
     launch_trsv_back(d, p->opt.use_mfma != 0, 1, p->stream);
-    HIPCK(p, plba_stream_wait(p->stream));
+    HIPCK(p, plba_stream_wait(p, p->stream));
     HIPCK(p, hipGetLastError());
     HIPCK(p, plba_d2h(p, x, xx.p, (size_t)n * 8));
     HIPCK(p, plba_d2h(p, &c0, ctrl.p, sizeof c0));
@@ -845,8 +850,12 @@ __global__ void k_prior_scatter(const double* __restrict__ H, int n, int nv, con
     }
     if (dr >= 0 && dc >= 0) Hconst[(size_t)dr * ld + dc] = H[t];
 }
-static int prepare(plba_problem* p) {
+// reads_prior: the caller consumes the prior (plba_optimize, plba_marginalize*, plba_debug_build): a prior that plba_marginalize_to_prior
+// changed on an unchanged window rebuilds it, as plba_set_prior would.  The other callers (results, gating, culling) keep the resident window.
+static int prepare(plba_problem* p, bool reads_prior = false) {
+    if (reads_prior && p->prior_changed) p->dirty = true;
     if (!p->dirty) return PLBA_OK;
+    if (p->mp) { if (int rc = marg_resolve(p)) return rc; }      // the prior this window reads (plba_marginalize_to_prior)
     if (!p->have_cam || !p->K) FAIL(p, PLBA_ERR_STATE, "camera and keyframes must be set before optimize");
     if ((int)p->po_pt.size() != p->Ep) p->Ep = 0;
     HIPCK(p, hipSetDevice(p->device));
@@ -886,7 +895,7 @@ static int prepare(plba_problem* p) {
         DArr<double> dvote;
         HIPCK(p, dvote.upload(vote)); HIPCK(p, darr_flush());
         if (int xrc = p->xfn(p->xuser, dvote.p, vote.size(), 0, (void*)p->stream)) { snprintf(p->err, sizeof p->err, "all-reduce callback failed (%d)", xrc); return PLBA_ERR_EXCHANGE; }
-        HIPCK(p, plba_stream_wait(p->stream));
+        HIPCK(p, plba_stream_wait(p, p->stream));
         return PLBA_ERR_INVALID;      // (p->err holds this rank's finding)
     }
     if ((int)p->level.size() != E) p->level.assign(E, 0);
@@ -942,7 +951,7 @@ static int prepare(plba_problem* p) {
         DArr<double> dvote;
         HIPCK(p, dvote.upload(vote)); HIPCK(p, darr_flush());
         if (int xrc = p->xfn(p->xuser, dvote.p, vote.size(), 0, (void*)p->stream)) FAIL(p, PLBA_ERR_EXCHANGE, "all-reduce callback failed (%d)", xrc);
-        HIPCK(p, plba_stream_wait(p->stream));
+        HIPCK(p, plba_stream_wait(p, p->stream));
         HIPCK(p, plba_d2h(p, vote.data(), dvote.p, vote.size() * 8));
         E_window = (long)vote[0];
         lm_fits = vote[1] == 0.0;
@@ -1067,13 +1076,14 @@ static int prepare(plba_problem* p) {
         DArr<double> dcov;
         HIPCK(p, dcov.upload(cd)); HIPCK(p, darr_flush());
         if (int xrc = p->xfn(p->xuser, dcov.p, cd.size(), 1, (void*)p->stream)) FAIL(p, PLBA_ERR_EXCHANGE, "all-reduce callback failed (%d)", xrc);
-        HIPCK(p, plba_stream_wait(p->stream));
+        HIPCK(p, plba_stream_wait(p, p->stream));
         HIPCK(p, plba_d2h(p, cd.data(), dcov.p, cd.size() * 8));
         for (size_t t = 0; t < cd.size(); ++t) cov[t] = cd[t] != 0.0;
     }
     lap("pair lists (host)");
     // ---- prior bookkeeping ----------------------------------------------------------------------------------------
     std::vector<int32_t> pr_kf(p->pr_nv), pr_isb(p->pr_nv), pr_x0off(p->pr_nv), pr_off(p->pr_nv);
+    size_t pr_nx = 0;
     {
         std::map<int, std::pair<int, int>> by_vid;
         for (int k = 0; k < K; ++k) { by_vid[p->vid_pvr[k]] = {k, 0}; if (p->vid_bias[k] >= 0) by_vid[p->vid_bias[k]] = {k, 1}; }
@@ -1086,7 +1096,10 @@ static int prepare(plba_problem* p) {
             pr_x0off[i] = xo; xo += p->pr_size[i] == 9 ? 10 : 6;
             pr_off[i] = pr_isb[i] ? p->off_bias[pr_kf[i]] : p->off_pvr[pr_kf[i]];
         }
+        pr_nx = (size_t)xo;
     }
+    // a prior made by plba_marginalize_to_prior: its numbers [x0 | J0 | r0 | ...] are read where the install left them
+    const double* pr_dev = p->prior_dev && p->pr_nv > 0 ? p->d_prd[p->prd_slot].p : nullptr;
     // ---- upload ----------------------------------------------------------------------------------------------------
     const size_t sysn = (size_t)(p->Ppad + TILE) * p->ld;
     if (p->carry_kf) {      // a slid window: the kept keyframes' states never left the device (plba_slide_window)
@@ -1163,7 +1176,7 @@ static int prepare(plba_problem* p) {
     HIPCK(p, p->d_imu_err.alloc((size_t)M * 16)); HIPCK(p, p->d_imu_chi.alloc((size_t)M * 4));
     HIPCK(p, p->d_pr_kf.upload(pr_kf)); HIPCK(p, p->d_pr_isbias.upload(pr_isb)); HIPCK(p, p->d_pr_size.upload(p->pr_size));
     HIPCK(p, p->d_pr_idx.upload(p->pr_idx)); HIPCK(p, p->d_pr_x0off.upload(pr_x0off)); HIPCK(p, p->d_pr_off.upload(pr_off));
-    HIPCK(p, p->d_pr_x0.upload(p->pr_x0)); HIPCK(p, p->d_pr_J0.upload(p->pr_J0)); HIPCK(p, p->d_pr_r0.upload(p->pr_r0));
+    if (!pr_dev) { HIPCK(p, p->d_pr_x0.upload(p->pr_x0)); HIPCK(p, p->d_pr_J0.upload(p->pr_J0)); HIPCK(p, p->d_pr_r0.upload(p->pr_r0)); }
     HIPCK(p, p->d_pr_err.alloc(p->pr_n)); HIPCK(p, p->d_pr_dx.alloc(p->pr_n)); HIPCK(p, p->d_pr_chi.alloc(1));
     HIPCK(p, p->d_Hconst.alloc((size_t)p->Ppad * p->ld)); HIPCK(p, p->d_Himu.alloc((size_t)p->Ppad * p->ld)); HIPCK(p, p->d_Himu2.alloc((size_t)p->Ppad * p->ld)); HIPCK(p, p->d_bimu2.alloc(p->ld));
     HIPCK(p, p->d_bprior.alloc(p->ld)); HIPCK(p, p->d_bprior2.alloc(p->ld));
@@ -1204,6 +1217,7 @@ static int prepare(plba_problem* p) {
     d.pr_n = p->pr_n; d.pr_nv = p->pr_nv;
     d.pr_kf = p->d_pr_kf.p; d.pr_isbias = p->d_pr_isbias.p; d.pr_size = p->d_pr_size.p; d.pr_idx = p->d_pr_idx.p;
     d.pr_x0off = p->d_pr_x0off.p; d.pr_off = p->d_pr_off.p; d.pr_x0 = p->d_pr_x0.p; d.pr_J0 = p->d_pr_J0.p; d.pr_r0 = p->d_pr_r0.p;
+    if (pr_dev) { d.pr_x0 = pr_dev; d.pr_J0 = pr_dev + pr_nx; d.pr_r0 = pr_dev + pr_nx + (size_t)p->pr_n * p->pr_n; }
     d.pr_err = p->d_pr_err.p; d.pr_dx = p->d_pr_dx.p; d.pr_chi = p->d_pr_chi.p;
     d.Hconst = p->d_Hconst.p; d.Himu = p->d_Himu.p; d.bimu = p->d_bimu.p; d.Himu_alt = p->d_Himu2.p; d.bimu_alt = p->d_bimu2.p; d.bprior = p->d_bprior.p; d.bprior_alt = p->d_bprior2.p; d.sys = p->d_sys.p; d.Lfac = p->d_Lfac.p; d.bpg = p->d_bpg.p; d.x = p->d_x.p;
     d.Linv = p->d_Linv.p; d.flow_flags = p->d_flow_flags.p; d.LTblk = p->d_LT32.p; d.Linv32 = p->d_LT32.p; d.rdblk = p->d_rd32.p; d.fb = (p->opt.factor_block == 64) ? 64 : 32; d.chol_flags = p->d_chol_flags.p; d.flow = p->opt.factor_flow != 0; d.wide = p->opt.wide_steps != 0 && !d.flow;
@@ -1896,12 +1910,12 @@ static int prepare(plba_problem* p) {
         // through the bounce buffer — about a millisecond of EVERY BA call of the reference's steady state, which carries a prior.)
         const int n = p->pr_n;
         HIPCK(p, p->d_pr_H.alloc((size_t)n * n)); HIPCK(p, darr_flush());
-        launch_ata(p->d_pr_J0.p, n, n, p->d_pr_H.p, n, p->stream);
+        launch_ata(d.pr_J0, n, n, p->d_pr_H.p, n, p->stream);
         hipLaunchKernelGGL(k_prior_scatter, dim3((n * n + 255) / 256), dim3(256), 0, p->stream, p->d_pr_H.p, n, p->pr_nv, p->d_pr_off.p, p->d_pr_idx.p, p->d_pr_size.p, p->d_Hconst.p, p->ld);
         HIPCK(p, hipGetLastError());
     }
     HIPCK(p, darr_flush());
-    HIPCK(p, plba_stream_wait(p->stream));      // the uploads above were queued on the stream from host vectors that end here
+    HIPCK(p, plba_stream_wait(p, p->stream));      // the uploads above were queued on the stream from host vectors that end here
     lap("final stream sync");
     if (ptime) fprintf(stderr, "[prepare] %zu small buffers in the batch blocks: %.0f KB cleared, %.0f KB copied\n", p->batch.n_batched, p->batch.zused / 1024.0, p->batch.uused / 1024.0);
     // buffers this window did not re-create must not keep a pointer into the batch blocks, which now hold other buffers (the
@@ -1920,6 +1934,7 @@ static int prepare(plba_problem* p) {
     p->cur = 0;
     p->saved_valid = true;
     p->dirty = false;
+    p->prior_changed = false;
     ++p->state_epoch;
     return PLBA_OK;
 }
@@ -2129,7 +2144,7 @@ extern "C" {
 int plba_optimize(plba_problem* p, int max_iters, const volatile uint8_t* abort_flag, plba_stats* out) {
     if (!p) return PLBA_ERR_INVALID;
     auto t0 = std::chrono::steady_clock::now();
-    int rc = prepare(p);
+    int rc = prepare(p, true);
     if (rc) return rc;
     HIPCK(p, hipSetDevice(p->device));
     const DevBuf& d = p->dv;
@@ -2184,11 +2199,11 @@ int plba_optimize(plba_problem* p, int max_iters, const volatile uint8_t* abort_
                     launch_decide(d, lp, p->d_red.p, false, p->d_mail, seq, s);
                 } else launch_decide_n(d, lp, p->d_red.p, p->lv.ngrp, p->d_mail, seq, s);
                 MARK(p, 10);
-                if (p->opt.profile >= 2) HIPCK(p, plba_stream_wait(s));
+                if (p->opt.profile >= 2) HIPCK(p, plba_stream_wait(p, s));
                 else {
                     long spins = 0;
                     while (__atomic_load_n(&p->h_mail->seq, __ATOMIC_ACQUIRE) != seq) {
-                        if (++spins > (1L << 22)) { HIPCK(p, plba_stream_wait(s)); break; }
+                        if (++spins > (1L << 22)) { HIPCK(p, plba_stream_wait(p, s)); break; }
                     }
                 }
             } else {
@@ -2196,7 +2211,7 @@ int plba_optimize(plba_problem* p, int max_iters, const volatile uint8_t* abort_
                 if (jac_trial) { if ((rc = lm_enqueue_system(p, ds, trial, true))) return rc; spec = true; }      // gated on the device-side decision
                 long spins = 0;
                 while (__atomic_load_n(&p->h_mail->seq, __ATOMIC_ACQUIRE) != seq) {
-                    if (++spins > (1L << 22)) { HIPCK(p, plba_stream_wait(s)); break; }
+                    if (++spins > (1L << 22)) { HIPCK(p, plba_stream_wait(p, s)); break; }
                 }
             }
             if (__atomic_load_n(&p->h_mail->seq, __ATOMIC_ACQUIRE) != seq) FAIL(p, PLBA_ERR_DEVICE, "LM control block was not delivered by the device");
@@ -2288,13 +2303,13 @@ int plba_optimize(plba_problem* p, int max_iters, const volatile uint8_t* abort_
                 }
             }
             if (p->opt.profile >= 2) {
-                HIPCK(p, plba_stream_wait(s));        // every phase event must have completed before it is read
+                HIPCK(p, plba_stream_wait(p, s));        // every phase event must have completed before it is read
             } else {
                 // k_decide is the last kernel of the trial and writes the control block into mapped host memory
                 long spins = 0;
                 while (__atomic_load_n(&p->h_mail->seq, __ATOMIC_ACQUIRE) != seq) {
                     if (++spins > (1L << 22)) {           // ~ tens of ms: fall back to a real synchronisation (and surface any device error)
-                        HIPCK(p, plba_stream_wait(s));
+                        HIPCK(p, plba_stream_wait(p, s));
                         break;
                     }
                 }
@@ -2332,7 +2347,7 @@ int plba_optimize(plba_problem* p, int max_iters, const volatile uint8_t* abort_
     }
     spec_unconsumed = spec_unconsumed || p->spec_lin || p->spec_hll;
     p->spec_lin = false; p->spec_hll = false;      // an unconsumed one (abort / stop right after an accepted step) only refreshed the records of the current state
-    if (spec_unconsumed) HIPCK(p, plba_stream_wait(s));      // the call returns with its stream drained (plba_stats.ms_total, plba.h)
+    if (spec_unconsumed) HIPCK(p, plba_stream_wait(p, s));      // the call returns with its stream drained (plba_stats.ms_total, plba.h)
     if (p->opt.profile == 1 && fact_samples > 0) st.ms_phase[1] = fact_sampled_ms / fact_samples * st.trials;      // sampled trials scaled to all
     if (abort_flag && *abort_flag && st.stop_reason == 0 && st.iterations < max_iters) st.stop_reason = 2;
     // trace + stats
@@ -2351,7 +2366,7 @@ int plba_optimize(plba_problem* p, int max_iters, const volatile uint8_t* abort_
         if (p->world > 1 && (rc = exchange(p, p->d_red.p, 1, 0))) return rc;
         double chi = 0.0;
         HIPCK(p, plba_d2h(p, &chi, p->d_red.p, 8));
-        HIPCK(p, plba_stream_wait(s));
+        HIPCK(p, plba_stream_wait(p, s));
         st.chi2_initial = st.chi2_final = chi;
     }
     (void)last_chi;
@@ -2367,7 +2382,7 @@ int plba_recompute_errors(plba_problem* p) {
     HIPCK(p, hipSetDevice(p->device));
     launch_linearize(p->dv, p->cur, false, p->rob, owns_pose_edges(p), p->stream);
     p->lm_chi_dirty = false;      // (ob_chi2 was just rewritten in place)
-    HIPCK(p, plba_stream_wait(p->stream));
+    HIPCK(p, plba_stream_wait(p, p->stream));
     return PLBA_OK;
 }
 
@@ -2378,7 +2393,7 @@ int plba_set_levels(plba_problem* p, plba_edge_kind kind, const uint8_t* level) 
     if ((int)p->level.size() != E) p->level.assign(E, 0);
     if (!p->dirty) {   // device copy may have been changed by gate_outliers: refresh the host mirror first
         HIPCK(p, hipSetDevice(p->device));
-        HIPCK(p, plba_stream_wait(p->stream));
+        HIPCK(p, plba_stream_wait(p, p->stream));
         if (E) HIPCK(p, plba_d2h(p, p->level.data(), p->d_level.p, E));
     }
     if (kind == PLBA_EDGE_POINT) memcpy(p->level.data(), level, p->Ep);
@@ -2393,7 +2408,7 @@ int plba_get_levels(plba_problem* p, plba_edge_kind kind, uint8_t* level) {
     if ((int)p->level.size() != E) p->level.assign(E, 0);
     if (!p->dirty && E) {
         HIPCK(p, hipSetDevice(p->device));
-        HIPCK(p, plba_stream_wait(p->stream));
+        HIPCK(p, plba_stream_wait(p, p->stream));
         HIPCK(p, plba_d2h(p, p->level.data(), p->d_level.p, E));
     }
     if (kind == PLBA_EDGE_POINT) memcpy(level, p->level.data(), p->Ep);
@@ -2413,7 +2428,7 @@ int plba_gate_outliers(plba_problem* p, double thresh, int* np_out, int* nl_out)
     launch_gate(d, p->cur, thresh, p->stream);
     if (p->lm_ok) launch_lm_level_sync(d, p->lv, p->stream);      // the fused passes read the levels in group order
     HIPCK(p, hipMemcpyAsync(p->h_ctrl, d.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, p->stream));
-    HIPCK(p, plba_stream_wait(p->stream));
+    HIPCK(p, plba_stream_wait(p, p->stream));
     p->rob.on[PLBA_EDGE_POINT] = 0;    // setRobustKernel(0) on every point / line edge (mapHandler.cpp:6055,6065)
     p->rob.on[PLBA_EDGE_LINE] = 0;
     if (np_out) *np_out = p->h_ctrl->n_gate_pt;
@@ -2432,7 +2447,7 @@ int plba_cull_observations(plba_problem* p, double thresh, uint8_t* bad_point, u
     if (E) {
         lm_chi_sync(p);
         launch_cull(d, p->cur, thresh, p->d_depth.p, p->stream);
-        HIPCK(p, plba_stream_wait(p->stream));
+        HIPCK(p, plba_stream_wait(p, p->stream));
         HIPCK(p, plba_d2h(p, bad.data(), p->d_depth.p, (size_t)E));
     }
     int np = 0, nl = 0;
@@ -2510,7 +2525,7 @@ static int get_results(plba_problem* p, int what, double* xyz, double* lines, do
             HIPCK(p, hipGetLastError());
             if (st && st->base && tot * 8 <= st->xfer_cap()) {
                 HIPCK(p, hipMemcpyAsync(st->xfer(), p->d_lm_pack.p, tot * 8, hipMemcpyDeviceToHost, p->stream));
-                HIPCK(p, plba_stream_wait(p->stream));
+                HIPCK(p, plba_stream_wait(p, p->stream));
                 src = reinterpret_cast<const double*>(st->xfer());      // the requested part goes straight to the caller from here
                 memcpy(h.data(), src, tot * 8);
             } else HIPCK(p, plba_d2h(p, h.data(), p->d_lm_pack.p, tot * 8));
@@ -2780,7 +2795,7 @@ int plba_slide_window(plba_problem* p, const plba_slide* s, int32_t* point_map, 
         if (E1) hipLaunchKernelGGL(k_obs_carry_gather, dim3((E1 + 255) / 256), dim3(256), 0, p->stream, p->d_po_uv.p, p->d_lo_l.p, p->d_ob_w.p, Ep0, dadd.p, dadd.p + o_wp, dadd.p + o_l, dadd.p + o_wl,
                                    p->d_obs_carry_src.p, Ep1, El1, p->d_po_uv_c.p, p->d_lo_l_c.p, p->d_ob_w_c.p);
         HIPCK(p, hipGetLastError());
-        if (!own_stage) HIPCK(p, plba_stream_wait(p->stream));      // (shared staging area: every queued copy must have left it before prepare() writes it again)
+        if (!own_stage) HIPCK(p, plba_stream_wait(p, p->stream));      // (shared staging area: every queued copy must have left it before prepare() writes it again)
         p->carry_po = true; p->carry_lo = true; p->carry_obs_pending = true;
         p->po_uv.resize(2 * (size_t)Ep1); p->po_w.resize(Ep1); p->lo_l.resize(3 * (size_t)El1); p->lo_w.resize(El1);      // (stale: carry_po / carry_lo)
     }
@@ -2827,7 +2842,7 @@ int plba_slide_window(plba_problem* p, const plba_slide* s, int32_t* point_map, 
 
 int plba_marginalize(plba_problem* p, int first_kf, int max_edges, plba_prior* out) {
     if (!p || !out) return PLBA_ERR_INVALID;
-    int rc = prepare(p);
+    int rc = prepare(p, true);
     if (rc) return rc;
     HIPCK(p, hipSetDevice(p->device));
     return marginalize_device(p, first_kf, max_edges, out);
@@ -2835,11 +2850,53 @@ int plba_marginalize(plba_problem* p, int first_kf, int max_edges, plba_prior* o
 int plba_marginalize_factors(plba_problem* p, int n_imu, const int32_t* imu_edges, int n_pt, const int32_t* point_edges,
                              int n_ln, const int32_t* line_edges, int use_prior, int n_drop, const int32_t* drop_vid, plba_prior* out) {
     if (!p || !out || n_imu < 0 || n_pt < 0 || n_ln < 0 || n_drop < 0) return PLBA_ERR_INVALID;
-    int rc = prepare(p);
+    int rc = prepare(p, true);
     if (rc) return rc;
     HIPCK(p, hipSetDevice(p->device));
     std::vector<int> im(imu_edges, imu_edges + n_imu), pt(point_edges, point_edges + n_pt), ln(line_edges, line_edges + n_ln), dr(drop_vid, drop_vid + n_drop);
     return marginalize_factors_device(p, im, pt, ln, use_prior != 0, dr, out);
+}
+int plba_marginalize_to_prior(plba_problem* p, int first_kf, int max_edges, int32_t* out3) {
+    if (!p) return PLBA_ERR_INVALID;
+    if (p->world > 1) FAIL(p, PLBA_ERR_STATE, "plba_marginalize_to_prior: a sharded problem is not marginalized on the device");
+    if (first_kf < 0 || first_kf >= p->K) FAIL(p, PLBA_ERR_INVALID, "marginalize: first_kf out of range");      // (before prepare(): window and prior untouched)
+    int rc = prepare(p, true);      // (resolves the previous one: its result is this call's old prior)
+    if (rc) return rc;
+    HIPCK(p, hipSetDevice(p->device));
+    if ((rc = marginalize_device(p, first_kf, max_edges, nullptr))) return rc;
+    if (out3) { out3[0] = p->pr_n; out3[1] = p->pr_m; out3[2] = p->pr_nv; }
+    return PLBA_OK;
+}
+int plba_get_prior(plba_problem* p, plba_prior* out) {
+    if (!p || !out) return PLBA_ERR_INVALID;
+    memset(out, 0, sizeof *out);
+    if (p->mp) { if (int rc = marg_resolve(p)) return rc; }
+    if (p->pr_nv == 0) FAIL(p, PLBA_ERR_STATE, "plba_get_prior: the problem holds no prior");
+    const int n = p->pr_n, nv = p->pr_nv;
+    size_t nx = 0;
+    for (int i = 0; i < nv; ++i) nx += p->pr_size[i] == 9 ? 10 : 6;
+    std::vector<double> h;
+    if (p->prior_dev) {      // [x0 | J0 | r0 | A' | b'] in one read-back
+        HIPCK(p, hipSetDevice(p->device));
+        h.resize(nx + 2 * (size_t)n * n + 2 * (size_t)n);
+        HIPCK(p, plba_d2h(p, h.data(), p->d_prd[p->prd_slot].p, h.size() * 8));
+    }
+    out->n = n; out->m = p->prior_dev ? p->pr_m : 0; out->nv = nv;
+    out->vid = (int32_t*)calloc(nv + 1, 4); out->size = (int32_t*)calloc(nv + 1, 4); out->idx = (int32_t*)calloc(nv + 1, 4);
+    memcpy(out->vid, p->pr_vid.data(), (size_t)nv * 4); memcpy(out->size, p->pr_size.data(), (size_t)nv * 4); memcpy(out->idx, p->pr_idx.data(), (size_t)nv * 4);
+    out->x0 = (double*)calloc(nx + 1, 8); out->J0 = (double*)malloc(((size_t)n * n + 1) * 8); out->r0 = (double*)malloc((size_t)(n + 1) * 8);
+    if (p->prior_dev) {
+        const double* q = h.data();
+        memcpy(out->x0, q, nx * 8); q += nx;
+        memcpy(out->J0, q, (size_t)n * n * 8); q += (size_t)n * n;
+        memcpy(out->r0, q, (size_t)n * 8); q += n;
+        out->Ar = (double*)malloc(((size_t)n * n + 1) * 8); out->br = (double*)malloc((size_t)(n + 1) * 8);
+        memcpy(out->Ar, q, (size_t)n * n * 8); q += (size_t)n * n;
+        memcpy(out->br, q, (size_t)n * 8);
+    } else {
+        memcpy(out->x0, p->pr_x0.data(), nx * 8); memcpy(out->J0, p->pr_J0.data(), (size_t)n * n * 8); memcpy(out->r0, p->pr_r0.data(), (size_t)n * 8);
+    }
+    return PLBA_OK;
 }
 void plba_prior_free(plba_prior* pr) {
     if (!pr) return;
@@ -2850,7 +2907,7 @@ void plba_prior_free(plba_prior* pr) {
 // ---- diagnostics ------------------------------------------------------------------------------------------------------
 int plba_debug_build(plba_problem* p, double lambda, int do_solve) {
     if (!p) return PLBA_ERR_INVALID;
-    int rc = prepare(p);
+    int rc = prepare(p, true);
     if (rc) return rc;
     HIPCK(p, hipSetDevice(p->device));
     const DevBuf& d = p->dv;
@@ -2862,7 +2919,7 @@ int plba_debug_build(plba_problem* p, double lambda, int do_solve) {
         p->lv.dbg_out = 1; p->lv.ob_err = p->d_ob_err.p;
         if ((rc = lm_enqueue_first(p, 0))) return rc;
         p->lm_chi_dirty = true;
-        HIPCK(p, plba_stream_wait(p->stream));
+        HIPCK(p, plba_stream_wait(p, p->stream));
         HIPCK(p, plba_d2h(p, &c0, d.ctrl, sizeof c0));
         c0.lambda = lambda;
         HIPCK(p, plba_h2d(p, d.ctrl, &c0, sizeof c0));
@@ -2873,29 +2930,35 @@ int plba_debug_build(plba_problem* p, double lambda, int do_solve) {
         }
         p->lv.dbg_out = 0; p->lv.ob_err = nullptr;
         if (rc) return rc;
-        HIPCK(p, plba_stream_wait(p->stream));
+        HIPCK(p, plba_stream_wait(p, p->stream));
         HIPCK(p, plba_d2h(p, p->h_ctrl, d.ctrl, sizeof(Ctrl)));
         return PLBA_OK;
     }
     if ((rc = enqueue_linearize(p, true, 0))) return rc;
-    HIPCK(p, plba_stream_wait(p->stream));
+    HIPCK(p, plba_stream_wait(p, p->stream));
     HIPCK(p, plba_d2h(p, &c0, d.ctrl, sizeof c0));
     c0.lambda = lambda;
     HIPCK(p, plba_h2d(p, d.ctrl, &c0, sizeof c0));
     if ((rc = enqueue_solve(p, do_solve != 0, true))) return rc;
-    HIPCK(p, plba_stream_wait(p->stream));
+    HIPCK(p, plba_stream_wait(p, p->stream));
     HIPCK(p, plba_d2h(p, p->h_ctrl, d.ctrl, sizeof(Ctrl)));
     return PLBA_OK;
 }
 
 int plba_debug_get(plba_problem* p, const char* what, double* out, size_t cap, size_t* n) {
     if (!p || !what) return PLBA_ERR_INVALID;
+    const std::string w(what);
+    if (w == "host_waits") {      // (read without waiting for anything)
+        if (n) *n = 1;
+        if (out && cap) *out = (double)p->host_waits;
+        return PLBA_OK;
+    }
     if (p->dirty) FAIL(p, PLBA_ERR_STATE, "debug_get before debug_build/optimize");
+    if (w == "marg_path" && p->mp) { if (int rc = marg_resolve(p)) return rc; }      // (after the check: a refused call changes nothing)
     HIPCK(p, hipSetDevice(p->device));
-    HIPCK(p, plba_stream_wait(p->stream));
+    HIPCK(p, plba_stream_wait(p, p->stream));
     const DevBuf& d = p->dv;
     std::vector<double> v;
-    const std::string w(what);
     auto fetch = [&](const double* dev, size_t cnt, std::vector<double>& h) -> hipError_t {
         h.resize(cnt);
         return cnt ? plba_d2h(p, h.data(), dev, cnt * 8) : hipSuccess;

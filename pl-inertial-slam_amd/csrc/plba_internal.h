@@ -295,8 +295,11 @@ bool chain_schur_factors_tile0(const DevBuf& dd);
 void launch_trsv_back(const DevBuf& d, bool use_mfma, int epoch, hipStream_t s);      // x = L^-T y; epoch must differ from the previous call's
 void launch_ata(const double* A_colmajor, int rows, int cols, double* out_rowmajor, int ldo, hipStream_t s);  // A^T A
 
-// marginalization
+// marginalization.  out == nullptr: plba_marginalize_to_prior — the result becomes the problem's prior on the device and the call returns
+// once the work is enqueued (marg_resolve completes it; marg_discard waits for it and drops it)
 int marginalize_device(struct plba_problem* p, int first_kf, int max_edges, plba_prior* out);
 int marginalize_factors_device(struct plba_problem* p, const std::vector<int>& imu_edges, const std::vector<int>& pt_edges,
                                const std::vector<int>& ln_edges, bool use_prior, const std::vector<int>& drop_vid, plba_prior* out);
+int marg_resolve(struct plba_problem* p);
+void marg_discard(struct plba_problem* p);
 }  // namespace plba

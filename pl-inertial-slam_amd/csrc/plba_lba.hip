@@ -773,7 +773,7 @@ int plba_lba_visual(plba_problem* p, const plba_lba_options* opt, int K, const d
         HIPCK(p, Linv.alloc((size_t)(Ppad / TILE) * TILE * TILE)); HIPCK(p, flags.alloc(Ppad / TILE)); HIPCK(p, LT32.alloc((size_t)Ppad * 64)); HIPCK(p, rd32.alloc(Ppad));
         HIPCK(p, cflags.alloc((size_t)(Ppad / 32 + 2) * (Ppad / 32)));
         if (Ppad / 32 <= NINV_MAX_T) HIPCK(p, Ninv.alloc((size_t)2 * Ppad * ld));
-        HIPCK(p, plba_stream_wait(s));
+        HIPCK(p, plba_stream_wait(p, s));
     }
     LbaDev d; memset(&d, 0, sizeof d);
     d.K = K; d.Nkf = Nkf; d.Np = Np; d.Nl = Nl; d.Ep = Ep; d.El = El; d.P = P; d.Ppad = Ppad; d.ld = ld;
@@ -800,7 +800,7 @@ int plba_lba_visual(plba_problem* p, const plba_lba_options* opt, int K, const d
     p->mail_seq += (unsigned long long)std::max(opt->max_iters, 0) + 1;
 
     const bool ltime = (p->opt.diag & PLBA_DIAG_TIMING) != 0;
-    if (ltime) HIPCK(p, plba_stream_wait(s));
+    if (ltime) HIPCK(p, plba_stream_wait(p, s));
     const auto lt0 = std::chrono::steady_clock::now();
     auto grid = [](size_t n, int b) { return dim3((unsigned)((n + b - 1) / b)); };
     hipLaunchKernelGGL(k_lba_init, grid(Nkf, 64), dim3(64), 0, s, d);
@@ -827,7 +827,7 @@ int plba_lba_visual(plba_problem* p, const plba_lba_options* opt, int K, const d
             const unsigned long long want = seq - 1;
             long spins = 0;
             while (__atomic_load_n(const_cast<const unsigned long long*>(&hm->seq), __ATOMIC_ACQUIRE) < want) {      // (what the mailbox held before is <= seq0)
-                if (++spins > (1L << 22)) { HIPCK(p, plba_stream_wait(s)); break; }
+                if (++spins > (1L << 22)) { HIPCK(p, plba_stream_wait(p, s)); break; }
             }
             if (hm->c.done) stop = true;
         }

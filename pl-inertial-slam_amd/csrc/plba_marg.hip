@@ -26,6 +26,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <vector>
 
 #include "plba_problem.h"
@@ -161,8 +162,12 @@ __global__ void k_block_pinv(const double* A, int pos, const int* boff, const in
             out[i * MAXB + j] = acc;
         }
 }
+// Gate of the block-wise launches (plba_marginalize_to_prior): null, or the certificate's verdict word (k_cert_final, diag[6]); a gated
+// launch returns at once when the certificate failed, so that A, b and the stacked J stay untouched for the dense path at resolution.
+MDEV bool gated_off(const double* gate) { return gate && *gate == 0.0; }
 // Z[row][o + c] = sum_t A[row][o + t] Pinv_b[t][c]     (only the eliminated columns of Z are written)
-__global__ void k_block_Z(const double* A, int pos, const int* boff, const int* bsize, int nblk, const double* Pinv, double* Z) {
+__global__ void k_block_Z(const double* A, int pos, const int* boff, const int* bsize, int nblk, const double* Pinv, double* Z, const double* gate) {
+    if (gated_off(gate)) return;
     const int row = blockIdx.x * blockDim.x + threadIdx.x, bi = blockIdx.y;
     if (row >= pos || bi >= nblk) return;
     const int s = bsize[bi], o = boff[bi];
@@ -173,7 +178,8 @@ __global__ void k_block_Z(const double* A, int pos, const int* boff, const int* 
         Z[(size_t)row * pos + o + c] = acc;
     }
 }
-__global__ void k_block_Z1(const double* A, int pos, int o, int s, const double* P, double* Z) {      // one block at offset o; a thread per (row, column)
+__global__ void k_block_Z1(const double* A, int pos, int o, int s, const double* P, double* Z, const double* gate) {      // one block at offset o; a thread per (row, column)
+    if (gated_off(gate)) return;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= pos * s) return;
     const int row = i / s, c = i - row * s;
@@ -182,7 +188,8 @@ __global__ void k_block_Z1(const double* A, int pos, int o, int s, const double*
     Z[(size_t)row * pos + o + c] = acc;
 }
 // A[r][c] -= sum_{k in elim} Z[r][k] A[k][c],  b[r] -= sum Z[r][k] b[k]   for r, c in `rest`
-__global__ void k_schur_apply(double* A, double* b, int pos, const double* Z, const int* elim, int nelim, const uint8_t* is_rest) {
+__global__ void k_schur_apply(double* A, double* b, int pos, const double* Z, const int* elim, int nelim, const uint8_t* is_rest, const double* gate) {
+    if (gated_off(gate)) return;
     const int c = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y * blockDim.y + threadIdx.y;
     if (r >= pos || c > pos || !is_rest[r]) return;
     if (c < pos && !is_rest[c]) return;
@@ -953,7 +960,8 @@ constexpr int JLDS_MAX_N = 100;       // A' and V both in LDS: (100 * 101 + 100 
 constexpr int JLDS_MAX_N2 = 140;      // A' alone in LDS (140 * 141 doubles = 157,920 bytes), V in global memory: the reference's 12-keyframe
                                       // window keeps up to 11 x 9 + 6 = 105 dims (src/mapHandler.cpp:6109-6188)
 // eigen pseudo-inverse of the dropped keyframe block (<= 15 dims) of the system the landmarks have been eliminated from
-__global__ __launch_bounds__(256) void k_pose_pinv(const double* A, int pos, int o, int sz, double eps, double* Pinv) {
+__global__ __launch_bounds__(256) void k_pose_pinv(const double* A, int pos, int o, int sz, double eps, double* Pinv, const double* gate) {
+    if (gated_off(gate)) return;
     __shared__ double G[MAXB * MAXB], V[MAXB * MAXB], lam[MAXB];
     __shared__ int rot;
     for (int t = threadIdx.x; t < sz * sz; t += blockDim.x) {
@@ -983,7 +991,9 @@ __global__ __launch_bounds__(256) void k_pose_pinv(const double* A, int pos, int
 // the STORAGE: n = 105 > 100 put V into global memory and the reference's own window paid 3.2 ms per slide where the configs[3] shape
 // paid 1.2.  The live columns are compacted into an nl x nl problem (75 x 75 there: both A' and V in LDS, 74 instead of 104 rounds per
 // sweep); Vg is only used when even the live part exceeds the in-LDS limit.
-__global__ __launch_bounds__(1024) void k_marg_finish(const double* A, const double* b, int pos, int m, int n, double eps, double* outp, double* Vg, double* dbg, int dyn_bytes, int prerotate) {
+__global__ __launch_bounds__(1024) void k_marg_finish(const double* A, const double* b, int pos, int m, int n, double eps, double* outp, double* Vg, double* dbg, int dyn_bytes, int prerotate,
+                                                   const double* gate) {
+    if (gated_off(gate)) return;
     extern __shared__ __attribute__((aligned(16))) double s_dyn[];
     __shared__ int rot, s_nl;
     __shared__ int s_live[JLDS_MAX_N2];
@@ -1347,6 +1357,152 @@ void est_pvr(const double* s, double* o) {   // GetEstData: P, V, Quaterniond(Rw
 }
 void est_bias(const double* s, double* o) { for (int c = 0; c < 3; ++c) { o[c] = s[10 + c] + s[16 + c]; o[3 + c] = s[13 + c] + s[19 + c]; } }
 
+// ---- the device's x0 (plba_marginalize_to_prior) --------------------------------------------------------------------------------
+// est_pvr / est_bias on the device, bit for bit: the host build does not contract a * b - c * d into an FMA and the device build
+// would (HIP's default), so the rotation round trip is spelled out here with contraction off (q_to_R / R_to_q of plba_math.h).
+MDEV void est_pvr_dev(const double* s, double* o) {
+#pragma clang fp contract(off)
+    for (int c = 0; c < 6; ++c) o[c] = s[c];
+    const double qx = s[6], qy = s[7], qz = s[8], qw = s[9];
+    const double tx = 2 * qx, ty = 2 * qy, tz = 2 * qz;
+    const double twx = tx * qw, twy = ty * qw, twz = tz * qw;
+    const double txx = tx * qx, txy = ty * qx, txz = tz * qx;
+    const double tyy = ty * qy, tyz = tz * qy, tzz = tz * qz;
+    double a[9];
+    a[0] = 1 - (tyy + tzz); a[1] = txy - twz; a[2] = txz + twy;
+    a[3] = txy + twz; a[4] = 1 - (txx + tzz); a[5] = tyz - twx;
+    a[6] = txz - twy; a[7] = tyz + twx; a[8] = 1 - (txx + tyy);
+    double x, y, z, w, t = a[0] + a[4] + a[8];
+    if (t > 0.0) {
+        t = sqrt(t + 1.0); w = 0.5 * t; t = 0.5 / t;
+        x = (a[7] - a[5]) * t; y = (a[2] - a[6]) * t; z = (a[3] - a[1]) * t;
+    } else if (a[0] >= a[4] && a[0] >= a[8]) {
+        t = sqrt(a[0] - a[4] - a[8] + 1.0); x = 0.5 * t; t = 0.5 / t;
+        w = (a[7] - a[5]) * t; y = (a[3] + a[1]) * t; z = (a[6] + a[2]) * t;
+    } else if (a[4] > a[0] && a[4] >= a[8]) {
+        t = sqrt(a[4] - a[8] - a[0] + 1.0); y = 0.5 * t; t = 0.5 / t;
+        w = (a[2] - a[6]) * t; z = (a[7] + a[5]) * t; x = (a[1] + a[3]) * t;
+    } else {
+        t = sqrt(a[8] - a[0] - a[4] + 1.0); z = 0.5 * t; t = 0.5 / t;
+        w = (a[3] - a[1]) * t; x = (a[2] + a[6]) * t; y = (a[5] + a[7]) * t;
+    }
+    o[6] = x; o[7] = y; o[8] = z; o[9] = w;
+}
+// The install: the prior slot dst = [x0 (nx) | J0 (n x n) | r0 (n) | A' (n x n) | b' (n)].  x0 from the keyframe states as the stream has
+// them at this point (before any slide moves them); J0, r0, A', b' from the output of k_marg_finish / k_eigen_sqrt res = [A' | b' | J0 | r0].
+// desc: per kept vertex [keyframe, is bias, offset in x0].
+__global__ __launch_bounds__(256) void k_prior_install(const double* kf, const int* desc, int nv, const double* res, int n, size_t nx, double* dst, int do_x0, int do_num) {
+    const int tid = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+    if (do_x0)
+        for (int v = tid; v < nv; v += stride) {
+            const double* st = kf + (size_t)desc[3 * v] * KF_STRIDE;
+            double* o = dst + desc[3 * v + 2];
+            if (desc[3 * v + 1]) { for (int c = 0; c < 3; ++c) { o[c] = st[10 + c] + st[16 + c]; o[3 + c] = st[13 + c] + st[19 + c]; } }
+            else est_pvr_dev(st, o);
+        }
+    if (!do_num) return;
+    const size_t nn = (size_t)n * n;
+    double* J0 = dst + nx; double* r0 = J0 + nn; double* Ar = r0 + n; double* br = Ar + nn;
+    for (size_t i = tid; i < nn; i += stride) { J0[i] = res[nn + n + i]; Ar[i] = res[i]; }
+    for (int i = tid; i < n; i += stride) { r0[i] = res[2 * nn + n + i]; br[i] = res[nn + i]; }
+}
+
+}  // namespace
+
+// The device buffers of one marginalization.  plba_marginalize keeps them on its stack until its one synchronisation; a
+// plba_marginalize_to_prior hands them to the problem (plba_problem::mp) — they must not go back to the process-wide pool while the
+// stream may still write them — together with what its resolution needs.
+struct MargPending {
+    DArr<double> dJ, dr, dA, db, dZ, dPinvL, dPinvP, dOut, dG, dV, dVm, dLam, dY, dCertD;
+    DArr<MargObs> dobs;
+    DArr<int> dboff, dbsize, delimL, delimP, dvcol, dimu, dCertI, dDesc;
+    DArr<uint8_t> drestL, drestP;
+    int R = 0, pos = 0, m = 0, n = 0, nv = 0, slot = 0;
+    size_t nout = 0, nx = 0;
+    double eps = 0.0;
+    bool gated = false;              // the certificate's verdict is decided on the device: read at resolution, dense path then if it failed
+    double* hres = nullptr;          // [certificate diag (7) | convergence word of k_marg_finish], written by queued copies (pinned)
+    std::vector<double> hres_pageable;
+    hipEvent_t ev = nullptr;         // behind the last queued operation
+    hipStream_t sync_stream = nullptr;      // set while the stream may still use the buffers: the destructor waits before they are released
+    ~MargPending() {
+        if (sync_stream) (void)hipStreamSynchronize(sync_stream);
+        if (ev) (void)hipEventDestroy(ev);
+    }
+};
+
+namespace {
+// (4) of the file comment: the eigen square root of the kept block into W.dOut.  gate: see gated_off.
+int marg_kept_block(plba_problem* p, MargPending& W, const double* gate, hipStream_t s) {
+    const int n = W.n, m = W.m, pos = W.pos;
+    double* oAr = W.dOut.p; double* obr = oAr + (size_t)n * n; double* oJ0 = obr + n; double* or0 = oJ0 + (size_t)n * n;
+    if (n <= JLDS_MAX_N2) {
+        // the live part of A' (its non-zero columns, known to the kernel only) decides whether V fits LDS next to it: the launch asks for the
+        // larger of the two layouts, and V gets a global buffer whenever n itself is beyond the in-LDS limit
+        const bool v_lds = n <= JLDS_MAX_N;
+        const size_t nl_max = std::min(n, JLDS_MAX_N);
+        size_t sh = std::max((size_t)n * (n | 1), nl_max * (nl_max | 1) + nl_max * nl_max) * sizeof(double);
+        // room for the one-barrier Jacobi's row tables behind A' and V, when the CU's LDS (160 KB less the kernel's static 4 KB) has it
+        const size_t sh_fast = (nl_max * (nl_max | 1) + nl_max * nl_max) * sizeof(double) + sizeof(Jac2sScratch);
+        if (std::max(sh, sh_fast) <= (size_t)163840 - 4096) sh = std::max(sh, sh_fast);
+        PLBA_HIPCK(p, ensure_dyn_lds(reinterpret_cast<const void*>(k_marg_finish), (int)sh));
+        if (!v_lds) PLBA_HIPCK(p, W.dV.alloc((size_t)n * n, false));
+        hipLaunchKernelGGL(k_marg_finish, dim3(1), dim3(1024), sh, s, W.dA.p, W.db.p, pos, m, n, W.eps, W.dOut.p, v_lds ? nullptr : W.dV.p, p->dv.dbgbuf, (int)sh,
+                           (p->opt.diag & PLBA_DIAG_NO_MARG_PREROTATE) ? 0 : 1, gate);
+    } else {
+        // larger kept blocks: G and V in HBM, one launch per round
+        PLBA_HIPCK(p, W.dG.alloc((size_t)n * n, false)); PLBA_HIPCK(p, W.dV.alloc((size_t)n * n, false));
+        const int nn_blocks = (int)(((size_t)n * n + 255) / 256);
+        hipLaunchKernelGGL(k_extract_cm, dim3(nn_blocks), dim3(256), 0, s, W.dA.p, pos, m, n, W.dG.p);
+        PLBA_HIPCK(p, hipMemcpyAsync(oAr, W.dG.p, (size_t)n * n * 8, hipMemcpyDeviceToDevice, s));      // symmetric: col-major == row-major
+        PLBA_HIPCK(p, hipMemcpyAsync(obr, W.db.p + m, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
+        if (int rc = jacobi_hbm(p, true, W.dG.p, n, W.dV.p, n, s)) return rc;
+        hipLaunchKernelGGL(k_eigen_sqrt, dim3((n + 63) / 64), dim3(64), 0, s, W.dG.p, W.dV.p, W.db.p + m, n, W.eps, oJ0, or0);
+    }
+    return PLBA_OK;
+}
+// the reference's own form of (3): eigen-decomposition of the whole Amm, eigenvalues <= eps discarded (cpp:351-362)
+int marg_dense_schur(plba_problem* p, MargPending& W, hipStream_t s) {
+    const int m = W.m, n = W.n, pos = W.pos;
+    // Amm = Jm^T Jm: the first m columns of the stacked Jacobian (no longer needed as such: A and b are formed) are rotated in place
+    PLBA_HIPCK(p, W.dVm.alloc((size_t)m * m, false));
+    PLBA_HIPCK(p, W.dLam.alloc(2 * (size_t)m, false)); PLBA_HIPCK(p, W.dY.alloc((size_t)m * (n + 1), false));
+    if (int rc = jacobi_hbm(p, false, W.dJ.p, W.R, W.dVm.p, m, s)) return rc;
+    hipLaunchKernelGGL(k_eig_winv, dim3((m + 3) / 4), dim3(256), 0, s, W.dJ.p, W.R, m, W.eps, W.dLam.p, W.dLam.p + m);
+    hipLaunchKernelGGL(k_vt_amr, dim3((n + 1 + 63) / 64, m), dim3(64), 0, s, W.dVm.p, W.dA.p, W.db.p, pos, m, n, W.dY.p);
+    if (n > 0) hipLaunchKernelGGL(k_dense_schur, dim3((n + 1 + 63) / 64, n), dim3(64), 0, s, W.dA.p, W.db.p, pos, m, n, W.dY.p, W.dLam.p + m);
+    return PLBA_OK;
+}
+void launch_prior_install(plba_problem* p, MargPending& W, bool do_x0, hipStream_t s) {
+    const size_t work = std::max((size_t)W.n * W.n, (size_t)std::max(W.nv, 1));
+    const int blocks = (int)std::min<size_t>((work + 255) / 256, 64);
+    hipLaunchKernelGGL(k_prior_install, dim3(blocks), dim3(256), 0, s, p->dv.kf[p->cur], W.dDesc.p, W.nv, W.dOut.p, W.n, W.nx, p->d_prd[W.slot].p, do_x0 ? 1 : 0, 1);
+}
+// pinned staging of the enqueue-only call (HostCtx::marg_stage), grown on demand; null when none can be had
+StageArea* marg_stage(plba_problem* p, size_t need) {
+    if (!p->have_ctx) return nullptr;
+    if (!p->ctx.marg_stage) p->ctx.marg_stage = new StageArea;
+    StageArea* ss = p->ctx.marg_stage;
+    if (ss->upload_cap() < need) {      // (no copy reads it: the previous marginalization has been resolved)
+        if (ss->base) { (void)hipHostFree(ss->base); ss->base = nullptr; ss->cap = 0; }
+        const size_t cap = std::max<size_t>((need + StageArea::XFER + ((size_t)1 << 20)) & ~(((size_t)1 << 20) - 1), (size_t)8 << 20);
+        if (hipHostMalloc((void**)&ss->base, cap, hipHostMallocDefault) == hipSuccess) ss->cap = cap; else ss->base = nullptr;
+    }
+    return ss->base && ss->upload_cap() >= need ? ss : nullptr;
+}
+void drop_prior(plba_problem* p) {
+    p->pr_n = p->pr_nv = 0; p->pr_m = 0; p->pr_vid.clear(); p->pr_size.clear(); p->pr_idx.clear();
+    p->pr_x0.clear(); p->pr_J0.clear(); p->pr_r0.clear();
+    p->prior_dev = false; p->prior_changed = true;
+}
+// every return of a plba_marginalize_to_prior / its resolution once device work has begun, error or not, goes through here: an error
+// leaves the problem without a prior (include/plba.h, item 6) whatever step it came from
+struct DropPriorUnlessDone {
+    plba_problem* p; bool armed;
+    int ok() { armed = false; return PLBA_OK; }
+    ~DropPriorUnlessDone() { if (armed) drop_prior(p); }
+};
+
 }  // namespace
 
 #define PID_PT(i) ((1 << 28) + (i))
@@ -1355,9 +1511,12 @@ void est_bias(const double* s, double* o) { for (int c = 0; c < 3; ++c) { o[c] =
 // General form: explicit factor lists.  imu_edges[]: each contributes its PVR edge and its bias edge;
 // pt_edges / ln_edges: indices into the uploaded point / line observation arrays; drop_vid[]: keyframe vertices
 // (ids) to marginalize out.  The landmark of every listed observation is always dropped (drop_set {0} at the call site).
+// out == nullptr: plba_marginalize_to_prior (include/plba.h) — nothing is read back unless the certificate can not be decided on
+// the device (a kept block beyond the in-LDS limit) or the dense path / the dump is asked for; the result is installed as the prior.
 int marginalize_factors_device(plba_problem* p, const std::vector<int>& imu_edges, const std::vector<int>& pt_edges,
                                const std::vector<int>& ln_edges, bool use_prior, const std::vector<int>& drop_vid, plba_prior* out) {
-    memset(out, 0, sizeof *out);
+    const bool to_prior = out == nullptr;
+    if (out) memset(out, 0, sizeof *out);
     const DevBuf& d = p->dv;
     hipStream_t s = p->stream;
     auto dropped = [&](int vid) { return std::find(drop_vid.begin(), drop_vid.end(), vid) != drop_vid.end(); };
@@ -1421,15 +1580,32 @@ int marginalize_factors_device(plba_problem* p, const std::vector<int>& imu_edge
     }
     const int n = pos - m;
     for (auto& o : obs) { o.col_lm = col[o.col_lm]; o.col_kf = col[o.col_kf]; }
+    for (size_t bq = 0; bq < blk_size.size(); ++bq) if (blk_size[bq] != 3 && blk_size[bq] != 6) PLBA_FAIL(p, PLBA_ERR_INVALID, "marginalize: landmark block of %d dims", blk_size[bq]);
+    if (to_prior && kept.empty()) PLBA_FAIL(p, PLBA_ERR_STATE, "marginalize: nothing is kept, no prior to install");
+    DropPriorUnlessDone drop_on_error{p, to_prior};
     // ---- device work: every index list goes up before the first launch, one stream synchronisation at the end ----------------
-    DArr<double> dJ, dr, dA, db, dZ, dPinvL, dPinvP, dOut, dG, dV, dVm, dLam, dY, dCertD;
-    DArr<MargObs> dobs;
-    DArr<int> dboff, dbsize, delimL, delimP, dvcol, dimu, dCertI;
-    DArr<uint8_t> drestL, drestP;
-    struct SyncOnExit { hipStream_t s; ~SyncOnExit() { (void)hipStreamSynchronize(s); } } sync_on_exit{s};   // declared after the buffers: runs before they go back to the pool
-    DArrStreamScope staged(s, p->have_ctx ? p->ctx.stage : nullptr);      // prepare() has synchronised: the staging area is free again
+    // (plba_marginalize_to_prior: the buffers belong to the problem until the resolution, the uploads go through a pinned area of their own
+    // that the next prepare() does not touch, and nothing waits unless the path chosen on the host needs a read-back)
+    std::unique_ptr<MargPending> Wheap;
+    MargPending Wstack;
+    MargPending& W = to_prior ? *(Wheap = std::make_unique<MargPending>()) : Wstack;
+    DArr<double>& dJ = W.dJ; DArr<double>& dr = W.dr; DArr<double>& dA = W.dA; DArr<double>& db = W.db; DArr<double>& dZ = W.dZ;
+    DArr<double>& dPinvL = W.dPinvL; DArr<double>& dPinvP = W.dPinvP; DArr<double>& dOut = W.dOut; DArr<double>& dCertD = W.dCertD;
+    DArr<MargObs>& dobs = W.dobs;
+    DArr<int>& dboff = W.dboff; DArr<int>& dbsize = W.dbsize; DArr<int>& delimL = W.delimL; DArr<int>& delimP = W.delimP;
+    DArr<int>& dvcol = W.dvcol; DArr<int>& dimu = W.dimu; DArr<int>& dCertI = W.dCertI;
+    DArr<uint8_t>& drestL = W.drestL; DArr<uint8_t>& drestP = W.drestP;
+    struct SyncOnExit { hipStream_t s; ~SyncOnExit() { if (s) (void)hipStreamSynchronize(s); } } sync_on_exit{to_prior ? nullptr : s};   // declared after the buffers: runs before they go back to the pool
+    StageArea* own_stage = nullptr;
+    if (to_prior) {
+        W.sync_stream = s;      // (an error return below waits before the buffers go back to the pool)
+        const size_t need = obs.size() * sizeof(MargObs) + (imu_edges.size() * 6 + p->pr_nv + 3 * (size_t)pos + 3 * kept.size()) * 4 + 2 * (size_t)pos + 16 * 256;
+        own_stage = marg_stage(p, need);
+    }
+    DArrStreamScope staged(s, to_prior ? own_stage : (p->have_ctx ? p->ctx.stage : nullptr));      // prepare() has synchronised: the staging area is free again
     const int state = p->cur;
     const double eps = p->opt.marg_eps;
+    W.R = R; W.pos = pos; W.m = m; W.n = n; W.eps = eps;
     // host-side index vectors (alive until the final synchronisation: without a staging area the copies read them directly)
     std::vector<int> imu_desc, vcol, elimL, elimP;
     std::vector<uint8_t> restL(pos, 1), restP;
@@ -1441,13 +1617,13 @@ int marginalize_factors_device(plba_problem* p, const std::vector<int>& imu_edge
     for (size_t bq = 0; bq < blk_off.size(); ++bq) for (int t = 0; t < blk_size[bq]; ++t) { elimL.push_back(blk_off[bq] + t); restL[blk_off[bq] + t] = 0; }
     restP = restL;
     for (int t = 0; t < pose_size; ++t) { elimP.push_back(pose_off + t); restP[pose_off + t] = 0; }
-    for (size_t bq = 0; bq < blk_size.size(); ++bq) if (blk_size[bq] != 3 && blk_size[bq] != 6) PLBA_FAIL(p, PLBA_ERR_INVALID, "marginalize: landmark block of %d dims", blk_size[bq]);
     PLBA_HIPCK(p, dJ.alloc((size_t)R * pos)); PLBA_HIPCK(p, dr.alloc(R)); PLBA_HIPCK(p, dA.alloc((size_t)pos * pos, false)); PLBA_HIPCK(p, db.alloc(pos, false));
     PLBA_HIPCK(p, dZ.alloc((size_t)pos * pos)); PLBA_HIPCK(p, dobs.upload(obs)); PLBA_HIPCK(p, dimu.upload(imu_desc)); PLBA_HIPCK(p, dvcol.upload(vcol));
     PLBA_HIPCK(p, dboff.upload(blk_off)); PLBA_HIPCK(p, dbsize.upload(blk_size)); PLBA_HIPCK(p, delimL.upload(elimL)); PLBA_HIPCK(p, delimP.upload(elimP));
     PLBA_HIPCK(p, drestL.upload(restL)); PLBA_HIPCK(p, drestP.upload(restP));
     PLBA_HIPCK(p, dPinvL.alloc(std::max<size_t>(blk_off.size(), 1) * MAXB * MAXB, false)); PLBA_HIPCK(p, dPinvP.alloc(MAXB * MAXB, false));
     const size_t nout = 2 * (size_t)n * n + 2 * (size_t)n + 1;      // [A' | b' | J0 | r0 | convergence word of k_marg_finish]
+    W.nout = nout;
     PLBA_HIPCK(p, dOut.alloc(nout));
     // (1) factors -> stacked Jacobian
     if (prior_row >= 0) launch_pose_edges(d, state, false, p->rob, true, s);       // refreshes pr_err = EdgeMarginalization::computeError at the final estimate
@@ -1474,6 +1650,9 @@ int marginalize_factors_device(plba_problem* p, const std::vector<int>& imu_edge
     if (mode < 0 || mode > 2) PLBA_FAIL(p, PLBA_ERR_INVALID, "marg_exact = %d (0 block-wise, 1 certified block-wise else dense, 2 dense)", mode);
     bool blockwise = mode != 2;
     const bool cert = mode == 1 && m > 0;
+    // the certificate decided on the device (plba_marginalize_to_prior, kept block in LDS): the block-wise launches are gated on its verdict
+    W.gated = to_prior && cert && n <= JLDS_MAX_N2;
+    const double* gate = nullptr;
     double cert_diag[7] = {0, 0, 0, 0, 0, 0, 0};
     constexpr int CERT_HDR = 8 + MAXB * MAXB + 8;      // [diag (8) | S(hi) (15 x 15) | arrival counter (8)] ahead of the per-block tables
     if (cert) {
@@ -1489,55 +1668,60 @@ int marginalize_factors_device(plba_problem* p, const std::vector<int>& imu_edge
         if (nb > 0) hipLaunchKernelGGL(k_cert_w, dim3(nb), dim3(64), 0, s, dA.p, pos, dboff.p, dbsize.p, cb);
         hipLaunchKernelGGL(k_cert_final, dim3(std::max(pose_size * pose_size, 1)), dim3(64), 0, s, dA.p, pos, pose_off, pose_size, dboff.p, dbsize.p, nb, hi, cb, dCertI.p, dCertD.p,
                            dCertD.p + 8, reinterpret_cast<unsigned*>(dCertD.p + 8 + MAXB * MAXB));
-        PLBA_HIPCK(p, plba_d2h(p, cert_diag, dCertD.p, sizeof cert_diag));      // (blocking: the one decision this call takes on the host)
-        blockwise = cert_diag[6] != 0.0;
+        if (W.gated) gate = dCertD.p + 6;
+        else {
+            PLBA_HIPCK(p, plba_d2h(p, cert_diag, dCertD.p, sizeof cert_diag));      // (blocking: the one decision this call takes on the host)
+            blockwise = cert_diag[6] != 0.0;
+        }
     }
-    p->marg_path[0] = blockwise ? 0.0 : 1.0;
-    for (int t = 0; t < 4; ++t) p->marg_path[1 + t] = cert_diag[t];
+    if (!W.gated) {      // (gated: known at resolution)
+        p->marg_path[0] = blockwise ? 0.0 : 1.0;
+        for (int t = 0; t < 4; ++t) p->marg_path[1 + t] = cert_diag[t];
+    }
     if (blockwise) {
         // landmark blocks, then the keyframe block of the reduced system
         if (nb > 0) {
-            hipLaunchKernelGGL(k_block_Z, dim3((pos + 63) / 64, nb), dim3(64), 0, s, dA.p, pos, dboff.p, dbsize.p, nb, dPinvL.p, dZ.p);
-            hipLaunchKernelGGL(k_schur_apply, dim3((pos + 1 + 15) / 16, (pos + 15) / 16), dim3(16, 16), 0, s, dA.p, db.p, pos, dZ.p, delimL.p, (int)elimL.size(), drestL.p);
+            hipLaunchKernelGGL(k_block_Z, dim3((pos + 63) / 64, nb), dim3(64), 0, s, dA.p, pos, dboff.p, dbsize.p, nb, dPinvL.p, dZ.p, gate);
+            hipLaunchKernelGGL(k_schur_apply, dim3((pos + 1 + 15) / 16, (pos + 15) / 16), dim3(16, 16), 0, s, dA.p, db.p, pos, dZ.p, delimL.p, (int)elimL.size(), drestL.p, gate);
         }
         if (pose_size > 0) {
-            hipLaunchKernelGGL(k_pose_pinv, dim3(1), dim3(256), 0, s, dA.p, pos, pose_off, pose_size, eps, dPinvP.p);
-            hipLaunchKernelGGL(k_block_Z1, dim3((pos * pose_size + 255) / 256), dim3(256), 0, s, dA.p, pos, pose_off, pose_size, dPinvP.p, dZ.p);
-            hipLaunchKernelGGL(k_schur_apply, dim3((pos + 1 + 15) / 16, (pos + 15) / 16), dim3(16, 16), 0, s, dA.p, db.p, pos, dZ.p, delimP.p, (int)elimP.size(), drestP.p);
+            hipLaunchKernelGGL(k_pose_pinv, dim3(1), dim3(256), 0, s, dA.p, pos, pose_off, pose_size, eps, dPinvP.p, gate);
+            hipLaunchKernelGGL(k_block_Z1, dim3((pos * pose_size + 255) / 256), dim3(256), 0, s, dA.p, pos, pose_off, pose_size, dPinvP.p, dZ.p, gate);
+            hipLaunchKernelGGL(k_schur_apply, dim3((pos + 1 + 15) / 16, (pos + 15) / 16), dim3(16, 16), 0, s, dA.p, db.p, pos, dZ.p, delimP.p, (int)elimP.size(), drestP.p, gate);
         }
     } else if (m > 0) {
-        // the reference's own form: eigen-decomposition of the whole Amm, eigenvalues <= eps discarded (cpp:351-362)
-        // Amm = Jm^T Jm: the first m columns of the stacked Jacobian (no longer needed as such: A and b are formed) are rotated in place
-        PLBA_HIPCK(p, dVm.alloc((size_t)m * m, false));
-        PLBA_HIPCK(p, dLam.alloc(2 * (size_t)m, false)); PLBA_HIPCK(p, dY.alloc((size_t)m * (n + 1), false));
-        if (int rc = jacobi_hbm(p, false, dJ.p, R, dVm.p, m, s)) return rc;
-        hipLaunchKernelGGL(k_eig_winv, dim3((m + 3) / 4), dim3(256), 0, s, dJ.p, R, m, eps, dLam.p, dLam.p + m);
-        hipLaunchKernelGGL(k_vt_amr, dim3((n + 1 + 63) / 64, m), dim3(64), 0, s, dVm.p, dA.p, db.p, pos, m, n, dY.p);
-        if (n > 0) hipLaunchKernelGGL(k_dense_schur, dim3((n + 1 + 63) / 64, n), dim3(64), 0, s, dA.p, db.p, pos, m, n, dY.p, dLam.p + m);
+        if (int rc = marg_dense_schur(p, W, s)) return rc;
     }
     // (4) eigen square root of the kept block
-    double* oAr = dOut.p; double* obr = oAr + (size_t)n * n; double* oJ0 = obr + n; double* or0 = oJ0 + (size_t)n * n;
-    if (n <= JLDS_MAX_N2) {
-        // the live part of A' (its non-zero columns, known to the kernel only) decides whether V fits LDS next to it: the launch asks for the
-        // larger of the two layouts, and V gets a global buffer whenever n itself is beyond the in-LDS limit
-        const bool v_lds = n <= JLDS_MAX_N;
-        const size_t nl_max = std::min(n, JLDS_MAX_N);
-        size_t sh = std::max((size_t)n * (n | 1), nl_max * (nl_max | 1) + nl_max * nl_max) * sizeof(double);
-        // room for the one-barrier Jacobi's row tables behind A' and V, when the CU's LDS (160 KB less the kernel's static 4 KB) has it
-        const size_t sh_fast = (nl_max * (nl_max | 1) + nl_max * nl_max) * sizeof(double) + sizeof(Jac2sScratch);
-        if (std::max(sh, sh_fast) <= (size_t)163840 - 4096) sh = std::max(sh, sh_fast);
-        PLBA_HIPCK(p, ensure_dyn_lds(reinterpret_cast<const void*>(k_marg_finish), (int)sh));
-        if (!v_lds) PLBA_HIPCK(p, dV.alloc((size_t)n * n, false));
-        hipLaunchKernelGGL(k_marg_finish, dim3(1), dim3(1024), sh, s, dA.p, db.p, pos, m, n, eps, dOut.p, v_lds ? nullptr : dV.p, d.dbgbuf, (int)sh, (p->opt.diag & PLBA_DIAG_NO_MARG_PREROTATE) ? 0 : 1);
-    } else {
-        // larger kept blocks: G and V in HBM, one launch per round
-        PLBA_HIPCK(p, dG.alloc((size_t)n * n, false)); PLBA_HIPCK(p, dV.alloc((size_t)n * n, false));
-        const int nn_blocks = (int)(((size_t)n * n + 255) / 256);
-        hipLaunchKernelGGL(k_extract_cm, dim3(nn_blocks), dim3(256), 0, s, dA.p, pos, m, n, dG.p);
-        PLBA_HIPCK(p, hipMemcpyAsync(oAr, dG.p, (size_t)n * n * 8, hipMemcpyDeviceToDevice, s));      // symmetric: col-major == row-major
-        PLBA_HIPCK(p, hipMemcpyAsync(obr, db.p + m, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
-        if (int rc = jacobi_hbm(p, true, dG.p, n, dV.p, n, s)) return rc;
-        hipLaunchKernelGGL(k_eigen_sqrt, dim3((n + 63) / 64), dim3(64), 0, s, dG.p, dV.p, db.p + m, n, eps, oJ0, or0);
+    if (int rc = marg_kept_block(p, W, gate, s)) return rc;
+    if (to_prior) {
+        // ---- install into the slot the current window's prior does not live in; two small queued read-backs for the resolution ---------
+        W.nv = (int)kept.size();
+        W.slot = p->prior_dev ? 1 - p->prd_slot : p->prd_slot;
+        std::vector<int> desc;
+        size_t nx = 0;
+        for (auto* k : kept) { desc.push_back(k->kf); desc.push_back(k->isbias); desc.push_back((int)nx); nx += k->size == 9 ? 10 : 6; }
+        W.nx = nx;
+        PLBA_HIPCK(p, W.dDesc.upload(desc));
+        PLBA_HIPCK(p, p->d_prd[W.slot].alloc(nx + 2 * (size_t)n * n + 2 * (size_t)n, false));
+        launch_prior_install(p, W, true, s);
+        W.hres = own_stage ? (double*)stage_take(8 * sizeof(double)) : nullptr;
+        if (!W.hres) { W.hres_pageable.assign(8, 0.0); W.hres = W.hres_pageable.data(); }
+        if (W.gated) PLBA_HIPCK(p, hipMemcpyAsync(W.hres, dCertD.p, 7 * sizeof(double), hipMemcpyDeviceToHost, s));
+        else memcpy(W.hres, cert_diag, sizeof cert_diag);
+        PLBA_HIPCK(p, hipMemcpyAsync(W.hres + 7, dOut.p + nout - 1, sizeof(double), hipMemcpyDeviceToHost, s));
+        PLBA_HIPCK(p, hipEventCreateWithFlags(&W.ev, hipEventDisableTiming));
+        PLBA_HIPCK(p, hipEventRecord(W.ev, s));
+        PLBA_HIPCK(p, hipGetLastError());
+        if (!own_stage) PLBA_HIPCK(p, plba_stream_wait(p, s));      // (no pinned area: the copies read pageable memory that ends here)
+        // ---- the host's half of the result is the problem's prior metadata from now on ----------------------------------------------------
+        p->pr_n = n; p->pr_nv = (int)kept.size(); p->pr_m = m;
+        p->pr_vid.resize(kept.size()); p->pr_size.resize(kept.size()); p->pr_idx.resize(kept.size());
+        for (size_t i = 0; i < kept.size(); ++i) { p->pr_vid[i] = kept[i]->pid; p->pr_size[i] = kept[i]->size; p->pr_idx[i] = col[kept[i]->pid] - m; }
+        p->pr_x0.clear(); p->pr_J0.clear(); p->pr_r0.clear();
+        p->prior_dev = true; p->prd_slot = W.slot; p->prior_changed = true;
+        p->mp = Wheap.release();
+        return drop_on_error.ok();
     }
     // ---- results: two asynchronous copies into pinned memory (the staging area's free tail), ONE synchronisation -------------
     const size_t nkf = (size_t)p->K * KF_STRIDE;
@@ -1551,7 +1735,7 @@ int marginalize_factors_device(plba_problem* p, const std::vector<int>& imu_edge
     }
     PLBA_HIPCK(p, hipMemcpyAsync(hres, dOut.p, nout * 8, hipMemcpyDeviceToHost, s));
     PLBA_HIPCK(p, hipMemcpyAsync(hres + nout, d.kf[state], nkf * 8, hipMemcpyDeviceToHost, s));
-    PLBA_HIPCK(p, plba_stream_wait(s));
+    PLBA_HIPCK(p, plba_stream_wait(p, s));
     PLBA_HIPCK(p, hipGetLastError());
     if (hres[nout - 1] >= 2.0) PLBA_FAIL(p, PLBA_ERR_NUMERIC, "marginalize: the Jacobi eigen-decomposition of the kept %d x %d block hit its sweep limit", n, n);
     // ---- output (host buffers owned by the caller until plba_prior_free) ----------------------------------------------------------
@@ -1573,6 +1757,48 @@ int marginalize_factors_device(plba_problem* p, const std::vector<int>& imu_edge
         if (k->size == 9) { est_pvr(st, out->x0 + nx); nx += 10; } else { est_bias(st, out->x0 + nx); nx += 6; }
     }
     return PLBA_OK;
+}
+
+// The first consumer of a plba_marginalize_to_prior's result completes it: the certificate's verdict and the convergence word are read
+// (queued into pinned memory at enqueue; normally long arrived), a failed certificate runs the dense path now — A, b and the stacked J are
+// as the call left them, since only the gated launches modify them — and an error of either surfaces here with the text plba_marginalize
+// uses.  After an error the problem holds no prior.
+int marg_resolve(plba_problem* p) {
+    MargPending* W = p->mp;
+    if (!W) return PLBA_OK;
+    p->mp = nullptr;
+    std::unique_ptr<MargPending> own(W);
+    DropPriorUnlessDone drop_on_error{p, true};
+    PLBA_HIPCK(p, hipSetDevice(p->device));
+    ++p->host_waits;
+    if (hipEventQuery(W->ev) != hipSuccess) PLBA_HIPCK(p, hipEventSynchronize(W->ev));
+    W->sync_stream = nullptr;      // (everything of this marginalization has run: the buffers may go back to the pool)
+    double conv = W->hres[7];
+    if (W->gated) {
+        const bool blockwise = W->hres[6] != 0.0;
+        p->marg_path[0] = blockwise ? 0.0 : 1.0;
+        for (int t = 0; t < 4; ++t) p->marg_path[1 + t] = W->hres[t];
+        if (!blockwise) {
+            hipStream_t s = p->stream;
+            DArrStreamScope zero_fill_on(s, nullptr);
+            W->sync_stream = s;
+            if (int rc = marg_dense_schur(p, *W, s)) return rc;
+            if (int rc = marg_kept_block(p, *W, nullptr, s)) return rc;
+            launch_prior_install(p, *W, false, s);
+            PLBA_HIPCK(p, hipGetLastError());
+            PLBA_HIPCK(p, plba_d2h(p, &conv, W->dOut.p + W->nout - 1, sizeof(double)));
+            W->sync_stream = nullptr;
+        }
+    }
+    if (conv >= 2.0) PLBA_FAIL(p, PLBA_ERR_NUMERIC, "marginalize: the Jacobi eigen-decomposition of the kept %d x %d block hit its sweep limit", W->n, W->n);
+    return drop_on_error.ok();
+}
+// plba_set_prior / plba_destroy / a recycled handle: wait for a pending marginalization, release its buffers, drop its result
+void marg_discard(plba_problem* p) {
+    if (!p->mp) return;
+    (void)hipSetDevice(p->device);
+    delete p->mp;      // (its destructor waits for the stream)
+    p->mp = nullptr;
 }
 
 // Factor selection of the call site (src/mapHandler.cpp:6075-6188): first IMU edge, <= NUM+1 point edges and

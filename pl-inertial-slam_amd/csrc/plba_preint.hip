@@ -75,6 +75,6 @@ extern "C" int plba_preintegrate(plba_problem* p, int M, const int32_t* sample_s
                        gyr_meas_cov, acc_meas_cov, d_out.p);
     PLBA_HIPCK(p, hipGetLastError());
     PLBA_HIPCK(p, plba_d2h(p, out142, d_out.p, (size_t)M * PREINT_DOUBLES * 8));
-    PLBA_HIPCK(p, plba_stream_wait(s));
+    PLBA_HIPCK(p, plba_stream_wait(p, s));
     return PLBA_OK;
 }

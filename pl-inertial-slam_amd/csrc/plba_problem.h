@@ -200,6 +200,7 @@ struct DArr {
 }  // namespace plba
 
 namespace plba {
+struct MargPending;      // a plba_marginalize_to_prior still in the stream (plba_marg.hip)
 // host image of the fused landmark-major passes' group structure (build_lm_groups, plba_api.hip); kept with the cached context
 // (HostCtx) so that its tables are not re-allocated (and their pages not re-faulted) by every BA call
 struct LmHost {
@@ -230,6 +231,7 @@ struct HostCtx {           // per-problem runtime objects, cached across problem
     plba::StageArea* stage = nullptr;   // pinned upload staging (heap object: HostCtx is copied around by value)
     plba::LmHost* lm_host = nullptr;    // the group tables of the fused passes: megabytes whose pages a fresh problem would fault in again
     plba::StageArea* slide_stage = nullptr;   // pinned staging of plba_slide_window's uploads: its own area, so that the slide need not wait for them before prepare() re-uses `stage`
+    plba::StageArea* marg_stage = nullptr;    // pinned staging of plba_marginalize_to_prior's uploads and read-back words: they are still queued when the call returns
 };
 
 
@@ -294,6 +296,16 @@ struct plba_problem {
     int pr_n = 0, pr_nv = 0;
     std::vector<int32_t> pr_vid, pr_size, pr_idx;
     std::vector<double> pr_x0, pr_J0, pr_r0;
+    // plba_marginalize_to_prior: the prior's numbers [x0 | J0 | r0 | A' | b'] stay on the device, in one of two slots — the install writes the
+    // slot the current window's prior does not live in (k_marg_factors of the same call still reads that one).  pr_x0 / pr_J0 / pr_r0 are then
+    // empty; the metadata above (pr_n, pr_nv, pr_vid, pr_size, pr_idx) is the host's, set when the call is enqueued.
+    plba::DArr<double> d_prd[2];
+    int prd_slot = 0;                     // the slot of the current device-made prior
+    bool prior_dev = false;               // the current prior is device-made (d_prd[prd_slot])
+    bool prior_changed = false;           // the prior changed but the window did not: the next prepare() rebuilds (plba_slide_window stays allowed)
+    int pr_m = 0;                         // dropped dimension of the device-made prior (plba_get_prior)
+    plba::MargPending* mp = nullptr;      // the marginalization that makes it, while it may still be in the stream (resolved by its first consumer)
+    long host_waits = 0;                  // times the library blocked the calling thread on the device (plba_debug_get "host_waits")
     plba::Robust rob;
     // shard
     int rank = 0, world = 1;
@@ -402,6 +414,8 @@ inline hipError_t plba_stream_wait(hipStream_t s, double spin_ms = 50.0) {
     }
     return hipStreamSynchronize(s);
 }
+// ... on behalf of a problem: counted (plba_problem::host_waits)
+inline hipError_t plba_stream_wait(plba_problem* p, hipStream_t s) { ++p->host_waits; return plba_stream_wait(s); }
 
 // Copies between device memory and CALLER-OWNED (pageable) host memory go through the context's pinned staging area.
 // Handing a pageable pointer to hipMemcpy makes the runtime pin (register) those pages with the GPU for transfers above its
@@ -411,6 +425,7 @@ inline hipError_t plba_stream_wait(hipStream_t s, double spin_ms = 50.0) {
 // state, e.g. on whether another problem's host vectors were alive).  Pinned memory the library owns never goes back.
 inline hipError_t plba_d2h(plba_problem* p, void* dst, const void* src_dev, size_t bytes) {
     if (!bytes) return hipSuccess;
+    ++p->host_waits;
     plba::StageArea* st = p->have_ctx ? p->ctx.stage : nullptr;
     if (!st || !st->base || !st->xfer_cap()) { hipError_t e = hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyDeviceToHost, p->stream); return e != hipSuccess ? e : plba_stream_wait(p->stream); }
     for (size_t off = 0; off < bytes; off += st->xfer_cap()) {
@@ -424,6 +439,7 @@ inline hipError_t plba_d2h(plba_problem* p, void* dst, const void* src_dev, size
 }
 inline hipError_t plba_h2d(plba_problem* p, void* dst_dev, const void* src, size_t bytes) {
     if (!bytes) return hipSuccess;
+    ++p->host_waits;
     plba::StageArea* st = p->have_ctx ? p->ctx.stage : nullptr;
     if (!st || !st->base || !st->xfer_cap()) { hipError_t e = hipMemcpyAsync(dst_dev, src, bytes, hipMemcpyHostToDevice, p->stream); return e != hipSuccess ? e : plba_stream_wait(p->stream); }
     for (size_t off = 0; off < bytes; off += st->xfer_cap()) {
