@@ -3,7 +3,10 @@ enumerate: keyframe counts 3..70, landmark counts from a handful to thousands, t
 (wide groups) — in every mix, points only / lines
 only, with and without IMU edges, marginalization priors, fixed keyframes and fixed landmarks, gating between two stages, huge and
 tiny initial damping (rejections).  One line per case; exits non-zero on the first disagreement.
-    python tools/soak_fused.py [N] [seed]"""
+    python tools/soak_fused.py [N] [seed]
+SOAK_KNOBS=1: every case also draws options.lm_group_steps (0 = the host's sizing, or 1 .. 16 workgroup steps per landmark group) and
+options.chain_seg (0 = the cost model's choice, or 1 .. 8 keyframes per chain segment), from a generator of their own, so that the same seed
+gives the same windows with and without it."""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np
@@ -14,6 +17,8 @@ pkg = g.load_package()
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 FUSED = int(os.environ.get("SOAK_LM_FUSED", "2"))      # 0: the same cases on the record-based passes (to tell conditioning from a defect of the fused ones)
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 7)
+KNOBS = os.environ.get("SOAK_KNOBS") == "1"
+krng = np.random.default_rng((int(sys.argv[2]) if len(sys.argv) > 2 else 7) + 0x6A0B)
 bad = 0
 for case in range(N):
     K = int(rng.choice([3, 4, 5, 6, 8, 9, 12, 16, 17, 25, 33, 40, 51, 70]))
@@ -42,7 +47,11 @@ for case in range(N):
     if rng.integers(0, 4) == 0 and Nl:
         w["line_fixed"] = (rng.random(Nl) < 0.2).astype(np.uint8); tag.append("fixedln")
     lam = float(rng.choice([0.0, 0.0, 1e3, 1e-3]))
-    a = pkg.new_problem(lm_fused=FUSED, user_lambda_init=lam); a.upload_window(w)
+    knobs = {}
+    if KNOBS:
+        knobs = dict(lm_group_steps=int(krng.choice([0, 1, 2, 3, 4, 5, 8, 16])), chain_seg=int(krng.integers(0, 9)))
+        tag.append("steps%d+seg%d" % (knobs["lm_group_steps"], knobs["chain_seg"]))
+    a = pkg.new_problem(lm_fused=FUSED, user_lambda_init=lam, **knobs); a.upload_window(w)
     b = orc.new_problem(user_lambda_init=lam); b.upload_window(w)
     sa1, sb1 = a.optimize(4), b.optimize(4)
     ga, gb = a.gate_outliers(), b.gate_outliers()
