@@ -332,6 +332,46 @@ int  plba_get_prior(plba_problem* p, plba_prior* out);
  * IMU/marginalization.cpp:353,365-366 read it): replaces options.marg_eps for the following plba_marginalize* calls. */
 int  plba_set_marg_eps(plba_problem* p, double eps);
 
+/* ---- marginal covariances (g2o computeMarginals / Ceres Covariance / GTSAM Marginals) -------------------------------
+ * The uncertainty of the problem's current estimate: what plba_get_keyframes / plba_get_points / plba_get_lines return.
+ *  - Linearised with the edges plba_optimize would build: level-0 point / line edges with the same Huber weighting, the IMU
+ *    edges, the prior the problem holds at the call (a pending plba_marginalize_to_prior is resolved first) and the line
+ *    Jacobian of options.fix_line_position_jacobian (SURVEY B-Q1 by default).  lambda = 0.  A slid window is prepared first.
+ *  - Tangent spaces: a keyframe's 15 = the PVR vertex's own update (body-frame dp, dv, dphi, as kf_oplus_pvr applies it)
+ *    then the bias update (dbg, dba).  Points: world xyz.  Lines: the 6 endpoint coordinates sP eP.
+ *  - Landmark elimination without damping:
+ *      status 0: eliminated.  A point with >= 2 active edges by its 3 x 3 Hll.  A line with >= 2 active edges in the
+ *                4-dimensional subspace B = blockdiag(N, N), N a 3 x 2 orthonormal basis of the plane orthogonal to
+ *                d = (eP - sP) / |eP - sP| (each endpoint is constrained only across the line).  The reported 6 x 6 is
+ *                B Sigma_r B^T, of rank 4: the along-line variance of an endpoint is unbounded and is not reported.
+ *      status 1: fixed landmark: zero covariance; its edges still enter the pose side, as in the LM.
+ *      status 2: fewer than 2 active edges: NaN covariance, no contribution to the pose system (exact: with one 2-row
+ *                observation the landmark's Schur term is zero).
+ *      status 3: the reduced block's Cholesky met a pivot <= 1e-12 x its largest diagonal entry: NaN, excluded like 2.
+ *  - The pose system S = Hpp - sum_l Hpl Hll_r^-1 Hlp over the free dimensions, Sigma_pp = S^-1.  Rows and columns of a
+ *    fixed PVR or bias vertex (or of a keyframe without a bias vertex) are 0 in every block.  A pivot of the Cholesky factor of S
+ *    at or below 1e-14 x the same dimension's diagonal entry of S (or not finite): PLBA_ERR_NUMERIC, nothing is written,
+ *    plba_last_error names the keyframe slot of the failing pivot.  This catches a keyframe or a velocity without constraints
+ *    (exactly zero rows: a window without IMU edges is refused); a gauge freedom that roundoff leaves at a larger pivot (a window
+ *    with neither a fixed vertex nor a prior) is not guaranteed to be caught: such a window has no meaningful covariance.
+ *  - Landmarks: Sigma_ll = B (Hr^-1 + Hr^-1 Wr^T Sigma_pp Wr Hr^-1) B^T (B = I for points).
+ *  - The problem's state is left alone: a following plba_optimize is bit-identical to one without this call in between.
+ *    Two calls on the same state give identical bits.  The call blocks once, for the read-back (plba_debug_get("host_waits")).
+ *    The dense part is the fp64 MFMA factorisation of the reduced camera system with its explicit inverse N = L^-T, then N N^T.
+ *  - Refused (changing nothing): a sharded problem (world > 1) or nothing uploaded: PLBA_ERR_STATE; a pair slot outside
+ *    [0, K), a negative n_pairs or a missing output buffer for a requested bit: PLBA_ERR_INVALID. */
+typedef struct plba_marginals {
+    int            want;        /* bit 0 keyframe blocks, bit 1 pair blocks, bit 2 points, bit 3 lines          */
+    int            n_pairs;     /* keyframe pairs whose cross-covariance is wanted                              */
+    const int32_t* pairs;       /* [n_pairs][2] keyframe slots (upload order), any order, repeats allowed        */
+    double*  kf_cov;            /* [K][15][15]   Cov(x_k), x_k = (dp dv dphi | bias update), row-major           */
+    double*  pair_cov;          /* [n_pairs][15][15]  Cov(x_i, x_j)                                              */
+    double*  pt_cov;  uint8_t* pt_status;   /* [Np][3][3], [Np] (status may be NULL)                               */
+    double*  ln_cov;  uint8_t* ln_status;   /* [Nl][6][6], [Nl]                                                    */
+    int32_t  n_excluded[2];     /* out: points / lines with status 2 or 3                                        */
+} plba_marginals;
+int plba_compute_marginals(plba_problem* p, plba_marginals* m);
+
 /* ---- IMU preintegration producer (upstream of plba_set_imu_edges) --------------------------
  * KeyFrame::ComputeIMUPreIntSinceLastFrame (src/keyFrame.cpp:139-172) for M keyframe intervals at once: per interval
  * IMUPreintegrator::reset (IMU/IMUPreintegrator.cpp:47-76), then one IMUPreintegrator::update (:80-139) per selected

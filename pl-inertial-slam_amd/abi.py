@@ -56,6 +56,13 @@ class LbaStats(C.Structure):
                 ("lam", C.c_double), ("solver_failed", C.c_int), ("reserved", C.c_int)]
 
 
+class Marginals(C.Structure):
+    """plba_marginals of include/plba.h"""
+    _fields_ = [("want", C.c_int), ("n_pairs", C.c_int), ("pairs", c_int32_p), ("kf_cov", c_double_p), ("pair_cov", c_double_p),
+                ("pt_cov", c_double_p), ("pt_status", c_uint8_p), ("ln_cov", c_double_p), ("ln_status", c_uint8_p),
+                ("n_excluded", C.c_int32 * 2)]
+
+
 class Slide(C.Structure):
     """plba_slide of include/plba.h"""
     _fields_ = [("n_drop", C.c_int), ("drop_point", c_uint8_p), ("drop_line", c_uint8_p), ("drop_point_obs", c_uint8_p), ("drop_line_obs", c_uint8_p),
@@ -75,7 +82,8 @@ _P = C.c_void_p  # plba_problem*
 
 # entry points of the product that have no counterpart in the reference's algorithm (memory management of the device-resident window): the
 # CPU oracle — a restatement of the reference — does not implement them
-PRODUCT_ONLY = {"slide_window", "get_sizes", "marginalize_to_prior", "get_prior"}
+# (compute_marginals: the reference computes no marginals; the oracle has no such entry)
+PRODUCT_ONLY = {"slide_window", "get_sizes", "marginalize_to_prior", "get_prior", "compute_marginals"}
 
 # name -> (restype, argtypes); every symbol plba.h declares
 SIGNATURES = {
@@ -117,6 +125,7 @@ SIGNATURES = {
     "marginalize_to_prior": (C.c_int, [_P, C.c_int, C.c_int, c_int32_p]),
     "get_prior": (C.c_int, [_P, C.POINTER(Prior)]),
     "prior_free": (None, [C.POINTER(Prior)]),
+    "compute_marginals": (C.c_int, [_P, C.POINTER(Marginals)]),
     "set_marg_eps": (C.c_int, [_P, C.c_double]),
     "lba_default_options": (None, [C.POINTER(LbaOptions)]),
     "lba_visual": (C.c_int, [_P, C.POINTER(LbaOptions), C.c_int, c_double_p, c_int32_p, C.c_int, c_double_p, C.c_int, c_double_p,
@@ -407,6 +416,30 @@ class Problem:
         self.call("marginalize_to_prior", int(first_kf), int(max_edges), _ip(out3))
         self.dims["n_prior"] = int(out3[0])
         return dict(n=int(out3[0]), m=int(out3[1]), nv=int(out3[2]))
+
+    def marginals(self, pairs=None, points=True, lines=True):
+        """plba_compute_marginals at the current estimate: dict of numpy arrays kf (K,15,15), pairs (n,15,15), pt (Np,3,3),
+        pt_status (Np,), ln (Nl,6,6), ln_status (Nl,) and n_excluded (points, lines)."""
+        sz = np.zeros(6, np.int32)
+        self.call("get_sizes", _ip(sz))
+        K, Np, Nl = int(sz[0]), int(sz[1]), int(sz[2])
+        pr = np.zeros((0, 2), np.int32) if pairs is None else np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+        kf = np.zeros((K, 15, 15)); pc = np.zeros((max(len(pr), 1), 15, 15))
+        pt = np.zeros((max(Np, 1), 3, 3)); ps = np.zeros(max(Np, 1), np.uint8)
+        ln = np.zeros((max(Nl, 1), 6, 6)); ls = np.zeros(max(Nl, 1), np.uint8)
+        m = Marginals()
+        m.want = 1 | (2 if len(pr) else 0) | (4 if points else 0) | (8 if lines else 0)
+        m.n_pairs = len(pr)
+        m.pairs = _ip(pr) if len(pr) else None
+        m.kf_cov, m.pair_cov, m.pt_cov, m.ln_cov = _dp(kf), _dp(pc), _dp(pt), _dp(ln)
+        m.pt_status, m.ln_status = _up(ps), _up(ls)
+        self.call("compute_marginals", C.byref(m))
+        out = dict(kf=kf, pairs=pc[:len(pr)], n_excluded=(int(m.n_excluded[0]), int(m.n_excluded[1])))
+        if points:
+            out["pt"], out["pt_status"] = pt[:Np], ps[:Np]
+        if lines:
+            out["ln"], out["ln_status"] = ln[:Nl], ls[:Nl]
+        return out
 
     def get_prior(self):
         """plba_get_prior: the current prior, as marginalize() returns it."""

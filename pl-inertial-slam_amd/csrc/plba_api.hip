@@ -2867,6 +2867,25 @@ int plba_marginalize_to_prior(plba_problem* p, int first_kf, int max_edges, int3
     if (out3) { out3[0] = p->pr_n; out3[1] = p->pr_m; out3[2] = p->pr_nv; }
     return PLBA_OK;
 }
+int plba_compute_marginals(plba_problem* p, plba_marginals* m) {
+    if (!p) return PLBA_ERR_INVALID;
+    if (!m) FAIL(p, PLBA_ERR_INVALID, "plba_compute_marginals: no plba_marginals");
+    if (p->world > 1) FAIL(p, PLBA_ERR_STATE, "plba_compute_marginals: a sharded problem has no marginals on the device");
+    if (!p->have_cam || !p->K) FAIL(p, PLBA_ERR_STATE, "plba_compute_marginals: nothing uploaded");
+    const bool want_pair = (m->want & 2) && m->n_pairs > 0;
+    if ((m->want & 2) && m->n_pairs < 0) FAIL(p, PLBA_ERR_INVALID, "plba_compute_marginals: n_pairs < 0");
+    if (want_pair && (!m->pairs || !m->pair_cov)) FAIL(p, PLBA_ERR_INVALID, "plba_compute_marginals: pairs / pair_cov missing");
+    if (want_pair)
+        for (int q = 0; q < 2 * m->n_pairs; ++q)
+            if (m->pairs[q] < 0 || m->pairs[q] >= p->K) FAIL(p, PLBA_ERR_INVALID, "plba_compute_marginals: pair %d names keyframe slot %d of %d", q / 2, m->pairs[q], p->K);
+    if ((m->want & 1) && !m->kf_cov) FAIL(p, PLBA_ERR_INVALID, "plba_compute_marginals: kf_cov missing");
+    if ((m->want & 4) && p->Np && !m->pt_cov) FAIL(p, PLBA_ERR_INVALID, "plba_compute_marginals: pt_cov missing");
+    if ((m->want & 8) && p->Nl && !m->ln_cov) FAIL(p, PLBA_ERR_INVALID, "plba_compute_marginals: ln_cov missing");
+    int rc = prepare(p, true);      // (slid window, pending prior: as plba_optimize would see them)
+    if (rc) return rc;
+    HIPCK(p, hipSetDevice(p->device));
+    return cov_run(p, m);
+}
 int plba_get_prior(plba_problem* p, plba_prior* out) {
     if (!p || !out) return PLBA_ERR_INVALID;
     memset(out, 0, sizeof *out);

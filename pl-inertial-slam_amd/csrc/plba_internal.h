@@ -301,5 +301,7 @@ int marginalize_device(struct plba_problem* p, int first_kf, int max_edges, plba
 int marginalize_factors_device(struct plba_problem* p, const std::vector<int>& imu_edges, const std::vector<int>& pt_edges,
                                const std::vector<int>& ln_edges, bool use_prior, const std::vector<int>& drop_vid, plba_prior* out);
 int marg_resolve(struct plba_problem* p);
+// marginal covariances at the current estimate (plba_cov.hip); the caller has checked the arguments and prepared the window
+int cov_run(struct plba_problem* p, plba_marginals* m);
 void marg_discard(struct plba_problem* p);
 }  // namespace plba

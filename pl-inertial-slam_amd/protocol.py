@@ -16,16 +16,20 @@ MAX_KF_IN_WINDOW = 12  # include/mapHandler.h:217
 
 
 def local_ba(prob, abort=None, stage1=STAGE1_ITERS, stage2=STAGE2_ITERS, chi2_gate=CHI2_GATE,
-             marginalize=False, first_kf=0, marg_num=MARG_NUM):
+             marginalize=False, first_kf=0, marg_num=MARG_NUM, marginals=False):
     """Run the two-stage local BA on an uploaded problem.  Returns a dict of per-stage stats, the
     gating counts and (if requested) the new prior.  marginalize="device": the new prior stays on the
-    device as the problem's own (plba_marginalize_to_prior); out["prior"] is then dict(n, m, nv)."""
+    device as the problem's own (plba_marginalize_to_prior); out["prior"] is then dict(n, m, nv).  marginals=True: the
+    marginal covariances of the final estimate (Problem.marginals) in out["marginals"], taken after stage 2 and before any
+    marginalization, where the call site holds this window's final estimate."""
     out = {}
     out["stage1"] = prob.optimize(stage1, abort)
     do_more = not (abort is not None and abort[0])                       # mapHandler.cpp:6043-6046
     if do_more:
         out["gated"] = prob.gate_outliers(chi2_gate)                     # :6047-6066
         out["stage2"] = prob.optimize(stage2, abort)                     # :6068-6069
+    if marginals:
+        out["marginals"] = prob.marginals()
     if marginalize == "device":                                          # :6075-6199, marg_info kept where it is made
         out["prior"] = prob.marginalize_to_prior(first_kf, marg_num)
     elif marginalize:                                                    # :6075-6199
