@@ -431,6 +431,33 @@ int plba_lba_visual(plba_problem* p, const plba_lba_options* opt, int K, const d
                     double fx, double fy, double cx, double cy, double* T_out16, uint8_t* pt_moved, uint8_t* ln_moved,
                     plba_lba_stats* stats);
 
+/* ---- loop-closure pose graph on the device ----------------------------------------------------------
+ * The optimiser part of loopClosureOptimizationCovGraphG2O / ...EssGraphG2O (src/mapHandler.cpp:4068-4528): g2o VertexSE3 /
+ * EdgeSE3 (include/plba_g2o/types_slam3d.h) under SparseOptimizer's Levenberg loop as the facade restates it (optimizeHost,
+ * include/plba_g2o/g2o_compat.h).  Vertices are addressed by their index and must be given in ascending vertex-id order (the
+ * Hessian order); only vertices some edge touches and that are not fixed are optimised; every other pose comes back bit for bit.
+ * Edges, assembly, LM control and the dense solve all run on the device; poses, stats and trace are read back once.
+ * initial_guess != 0: computeInitialGuess first (breadth first from the fixed vertices, edges in insertion order, on the host).
+ * user_lambda_init: g2o's userLambdaInit (the reference: 1e-10); 0 = options.tau * max diag(H).  The LM constants tau,
+ * max_trials and the good-step bounds come from the problem's options.  max_iters = 0 only evaluates chi2.
+ * Refused with PLBA_ERR_INVALID and pose12 untouched: nv <= 0, an index out of range, ei == ej, a non-finite input, a missing
+ * array or output.  The problem's uploaded window is neither read nor written. */
+typedef struct plba_pose_graph {
+    int            nv;          /* vertices                                                                           */
+    double*        pose12;      /* in/out [nv][12]: R row-major (9), t (3) of each VertexSE3 estimate (Isometry3)      */
+    const uint8_t* fixed;       /* [nv] 1 = fixed vertex; may be NULL (none fixed)                                    */
+    int            ne;          /* edges                                                                              */
+    const int32_t* ei;          /* [ne] vertex 0 of the edge (g2o: setVertex(0, ..))                                  */
+    const int32_t* ej;          /* [ne] vertex 1                                                                      */
+    const double*  meas12;      /* [ne][12] measurement Z, layout of pose12                                           */
+    const double*  info36;      /* [ne][36] row-major information; NULL = identity (the reference sets none)          */
+} plba_pose_graph;
+/* stats: iterations, trials, stop_reason (1 = LM Terminate), solver_failures, chi2_initial (after the initial guess),
+ * chi2_final, lambda_final, ms_total.  trace (may be NULL when trace_cap = 0): one row per trial, the first trace_cap of
+ * them; *n_trace (may be NULL) = the number of trials. */
+int plba_optimize_pose_graph(plba_problem* p, plba_pose_graph* g, int max_iters, double user_lambda_init, int initial_guess,
+                             plba_stats* stats, plba_trace_row* trace, int trace_cap, int* n_trace);
+
 /* ---- diagnostics used by the parity tests (not needed by a drop-in caller) ------------------- */
 /* Runs computeActiveErrors + buildSystem + setLambda(lambda) + Schur on the current state without
  * updating it, then exposes named internal buffers: "Hschur" (P*P row-major), "bschur" (P),

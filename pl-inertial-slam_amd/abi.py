@@ -76,14 +76,21 @@ class Slide(C.Structure):
                 ("El_add", C.c_int), ("lo_ln", c_int32_p), ("lo_kf", c_int32_p), ("l3", c_double_p), ("lo_inv_sigma2", c_double_p)]
 
 
+class PoseGraph(C.Structure):
+    """plba_pose_graph of include/plba.h"""
+    _fields_ = [("nv", C.c_int), ("pose12", c_double_p), ("fixed", c_uint8_p), ("ne", C.c_int), ("ei", c_int32_p), ("ej", c_int32_p),
+                ("meas12", c_double_p), ("info36", c_double_p)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
 
 _P = C.c_void_p  # plba_problem*
 
 # entry points of the product that have no counterpart in the reference's algorithm (memory management of the device-resident window): the
 # CPU oracle — a restatement of the reference — does not implement them
-# (compute_marginals: the reference computes no marginals; the oracle has no such entry)
-PRODUCT_ONLY = {"slide_window", "get_sizes", "marginalize_to_prior", "get_prior", "compute_marginals"}
+# (compute_marginals: the reference computes no marginals; the oracle has no such entry.  optimize_pose_graph: the oracle restates the
+# pose graph as orc_pgo, a checker entry of its own outside this table)
+PRODUCT_ONLY = {"slide_window", "get_sizes", "marginalize_to_prior", "get_prior", "compute_marginals", "optimize_pose_graph"}
 
 # name -> (restype, argtypes); every symbol plba.h declares
 SIGNATURES = {
@@ -135,6 +142,7 @@ SIGNATURES = {
     "debug_get": (C.c_int, [_P, C.c_char_p, c_double_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "dense_solve": (C.c_int, [_P, C.c_int, c_double_p, c_double_p, c_double_p, C.POINTER(C.c_int)]),
     "debug_dense_solve": (C.c_int, [_P, C.c_int, c_double_p, c_double_p, c_double_p, C.POINTER(C.c_int)]),
+    "optimize_pose_graph": (C.c_int, [_P, C.POINTER(PoseGraph), C.c_int, C.c_double, C.c_int, C.POINTER(Stats), C.POINTER(TraceRow), C.c_int, C.POINTER(C.c_int)]),
 }
 
 
@@ -504,6 +512,39 @@ class Problem:
 
     def debug_dense_solve(self, A, b):
         return self.dense_solve(A, b, entry="debug_dense_solve")
+
+    def pgo(self, pose12, ei, ej, meas12, info=None, fixed=None, iters=100, user_lambda=0.0, initial_guess=False, trace_cap=None):
+        """plba_optimize_pose_graph: g2o VertexSE3 / EdgeSE3 under the Levenberg loop, on the device.  pose12 (nv, 12) and meas12 (ne, 12):
+        R row-major, t; info (ne, 6, 6) or None (identity); fixed (nv,) or None.  Returns (poses (nv, 12), stats dict, trace list of dicts);
+        the problem's window is not touched."""
+        X = _f64(pose12)
+        if X.ndim != 2 or X.shape[1] != 12 or X.shape[0] < 1:
+            raise ValueError("pose12 must be (nv, 12), nv >= 1")
+        X = X.copy()
+        nv = X.shape[0]
+        ei, ej = _i32(np.asarray(ei).ravel()), _i32(np.asarray(ej).ravel())
+        Z = _f64(meas12)
+        ne = len(ei)
+        if len(ej) != ne or Z.size != 12 * ne:
+            raise ValueError("ei, ej and meas12 must describe the same %d edges" % ne)
+        Z = Z.reshape(ne, 12)
+        om = None if info is None else _f64(info).reshape(-1)
+        if om is not None and om.size != 36 * ne:
+            raise ValueError("info must be (ne, 6, 6)")
+        fx = None if fixed is None else _u8(np.asarray(fixed).astype(bool))
+        if fx is not None and fx.size != nv:
+            raise ValueError("fixed must have nv entries")
+        g = PoseGraph(nv, _dp(X), _up(fx), ne, _ip(ei), _ip(ej), _dp(Z), _dp(om))
+        cap = max(1, int(iters) * 10) if trace_cap is None else int(trace_cap)
+        rows = (TraceRow * max(cap, 1))()
+        st = Stats()
+        ntr = C.c_int(0)
+        self.call("optimize_pose_graph", C.byref(g), int(iters), float(user_lambda), 1 if initial_guess else 0, C.byref(st), rows, cap, C.byref(ntr))
+        stats = dict(iterations=st.iterations, trials=st.trials, stop_reason=st.stop_reason, solver_failures=st.solver_failures,
+                     chi2_initial=st.chi2_initial, chi2_final=st.chi2_final, lambda_final=st.lambda_final, ms_total=st.ms_total, n_trace=ntr.value)
+        trace = [dict(iteration=r.iteration, trial=r.trial, accepted=r.accepted, solver_ok=r.solver_ok, lam=r.lam, chi2_current=r.chi2_current,
+                      chi2_trial=r.chi2_trial, scale=r.scale, rho=r.rho) for r in rows[:min(ntr.value, cap)]]
+        return X, stats, trace
 
     def preintegrate(self, sample_start, t, gyr, acc, t_prev, t_curr, bg, ba, gyr_meas_cov, acc_meas_cov):
         """KeyFrame::ComputeIMUPreIntSinceLastFrame for M intervals (plba_preintegrate); time stamps as np.longdouble."""

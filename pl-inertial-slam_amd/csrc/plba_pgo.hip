@@ -1,0 +1,595 @@
+// plba_pgo.hip — SURVEY §8f row 4: the loop-closure pose graph of loopClosureOptimizationCovGraphG2O / ...EssGraphG2O
+// (src/mapHandler.cpp:4068-4528) on gfx950: g2o VertexSE3 / EdgeSE3 as include/plba_g2o/types_slam3d.h restates them, under
+// the Levenberg loop of SparseOptimizer::optimizeHost (include/plba_g2o/g2o_compat.h), edges to solve on the device.
+//
+// Layout (n free vertices = those an edge touches that are not fixed, in ascending vertex order; P = 6 n):
+//   X, Xs     nv x 12        estimates (R row-major, t) and the backup of the trial's free vertices; cnt: nv oplus counters
+//   erec      ne x 120       per edge  A00 = J0^T O J0 | A11 = J1^T O J1 | A10 = J1^T O J0 | g0 = J0^T O e | g1 = J1^T O e
+//   echi      ne             per edge  e^T O e of the last evaluation
+//   blocks    nblk           every nonzero 6 x 6 block of H (row vertex >= column vertex) with its (edge, slot) sources in edge
+//                            order, built once on the host; Hblk (nblk x 36) and b (P) = their undamped sums
+//   blkmap    n x n          block id * 2 (+ 1: the transposed block), -1: structurally zero
+//   sys       (Ppad + 64) x ld   the damped system in the layout launch_cholesky / launch_trsv_back take, b in row Ppad
+//
+// One STEP = one LM trial; the host enqueues steps and polls the mapped mailbox one step behind (it never waits on the step it
+// has just enqueued, so the device never idles on the host).  A step is
+//   k_pgo_edges<jac>      (only when an iteration starts)  error, Jacobians, weighted blocks per edge      thread per edge
+//   k_pgo_sum             (only when an iteration starts)  Hblk, b: each block's sources summed in edge order   wave per block
+//   k_pgo_iter            (only when an iteration starts)  currentChi, lambda init (computeLambdaInit)        one workgroup
+//   k_pgo_fill            sys = H + lambda I (both triangles), unit padding, b; the identity once the run is over
+//   launch_cholesky / launch_trsv_back (plba_dense.hip)   x, solver_ok
+//   k_pgo_update          backup, X <- X fromVectorMQT(x) (x = 0 after a failed factorisation), orthogonalizeAfter
+//   k_pgo_edges<errors>   the trial's chi2 per edge
+//   k_pgo_decide          tempChi, scale, rho, the g2o lambda schedule, restore on rejection, trace row, loop exits, mailbox
+// Every kernel but the factorisation returns at once after the run has ended (PgoCtl::done).  Nothing of O(P^2) or O(E)
+// crosses PCIe between the upload and the read-back of the poses, the control block and the trace.
+// Bit-reproducible: no floating-point atomics; every sum has one owner and a fixed order.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstddef>
+#include <cstring>
+#include <vector>
+
+#include "plba_internal.h"
+#include "plba_problem.h"
+
+#define HIPCK(p, call) PLBA_HIPCK(p, call)
+#define FAIL(p, code, ...) PLBA_FAIL(p, code, __VA_ARGS__)
+
+namespace plba {
+namespace {
+
+constexpr int PGO_REC = 120;          // per-edge record (see the layout above)
+constexpr int ORTHO_AFTER = 1000;  // VertexSE3::orthogonalizeAfter
+
+// device-side control: the Ctrl the factorisation reports solver_ok into, + the loop state of optimizeHost
+struct PgoCtl {
+    Ctrl c;                 // lambda, ni, current_chi, temp_chi, scale, rho, maxdiag; accepted, solver_ok, iteration, trial, n_fail
+    double chi2_initial, chi2_final, lambda_final;
+    int lin;                // 1: the next step starts an iteration (linearise, sum, currentChi)
+    int done, iters, trials, stop_reason, n_trace, pad0, pad1;
+};
+struct PgoHead { int done, iters, trials, pad; };
+struct PgoMail {            // laid over the problem's mapped Mailbox (plba_internal.h): same size, `seq` at the same offset
+    PgoHead h;
+    char pad[sizeof(Ctrl) - sizeof(PgoHead)];
+    unsigned long long seq;
+    char pad2[sizeof(Mailbox) - sizeof(Ctrl) - sizeof(unsigned long long)];
+};
+static_assert(sizeof(PgoHead) <= sizeof(Ctrl) && sizeof(PgoMail) == sizeof(Mailbox) && offsetof(PgoMail, seq) == offsetof(Mailbox, seq),
+              "the pose-graph mailbox reuses the problem's mapped mailbox");
+
+struct PgoDev {
+    int nv, ne, n, P, Ppad, ld, nblk, max_iters, max_trials, trace_cap;
+    double tau, lower, upper, user_lambda;
+    double* X;                  // nv x 12
+    double* Xs;                 // nv x 12 (free vertices only)
+    int* cnt;                   // nv
+    const int32_t* free_v;      // n: vertex of each free rank
+    const int32_t* ei;          // ne
+    const int32_t* ej;
+    const double* Zi;           // ne x 12: inverse measurements
+    const double* info;         // ne x 36
+    double* erec;               // ne x PGO_REC
+    double* echi;               // ne
+    const int32_t* blk_start;   // nblk + 1
+    const int32_t* blk_src;     // edge * 4 + slot (0 A00, 1 A11, 2 A10, 3 A10^T)
+    const int32_t* blk_diag;    // nblk: 1 = a diagonal block (carries b)
+    const int32_t* blk_row;     // nblk: free rank of the block row
+    const int32_t* dg_blk;      // n: diagonal block of each free rank
+    const int32_t* blkmap;      // n x n
+    double* Hblk;               // nblk x 36
+    double* b;                  // P
+    double* sys;
+    const double* x;            // dense solution
+    PgoCtl* ctl;
+    PgoMail* mail;
+    plba_trace_row* trace;
+};
+
+struct Iso { M3 R; V3 t; };
+__device__ __forceinline__ Iso iso_load(const double* p) {
+    Iso a;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) a.R.a[i] = p[i];
+    a.t = v3(p[9], p[10], p[11]);
+    return a;
+}
+__device__ __forceinline__ void iso_store(const Iso& a, double* p) {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) p[i] = a.R.a[i];
+    p[9] = a.t.x; p[10] = a.t.y; p[11] = a.t.z;
+}
+// slam3d_detail::mul / inv / from_mqt / unit_q of include/plba_g2o/types_slam3d.h, on the plba_math.h helpers
+__device__ __forceinline__ Iso iso_mul(const Iso& a, const Iso& b) { Iso r; r.R = mul(a.R, b.R); r.t = mul(a.R, b.t) + a.t; return r; }
+__device__ __forceinline__ Iso iso_inv(const Iso& a) { Iso r; r.R = transpose(a.R); const V3 x = mul(r.R, a.t); r.t = v3(-x.x, -x.y, -x.z); return r; }
+__device__ __forceinline__ Iso iso_from_mqt(const double* u) {
+    Iso r;
+    r.t = v3(u[0], u[1], u[2]);
+    const double w2 = 1.0 - (u[3] * u[3] + u[4] * u[4] + u[5] * u[5]);
+    if (w2 < 0) r.R = eye3();
+    else { Q4 q; q.x = u[3]; q.y = u[4]; q.z = u[5]; q.w = sqrt(w2); r.R = q_to_R(q); }
+    return r;
+}
+__device__ __forceinline__ Q4 unit_q(const M3& R) {
+    Q4 q = q_normalized(R_to_q(R));
+    if (q.w < 0) { q.x = -q.x; q.y = -q.y; q.z = -q.z; q.w = -q.w; }
+    return q;
+}
+
+// EdgeSE3::computeError (+ linearizeOplus and the weighted blocks of buildHost when JAC)
+template <bool JAC>
+__global__ __launch_bounds__(64) void k_pgo_edges(PgoDev d) {
+    if (d.ctl->done || (JAC && !d.ctl->lin)) return;
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    if (k >= d.ne) return;
+    const Iso Xi = iso_load(d.X + (size_t)12 * d.ei[k]), Xj = iso_load(d.X + (size_t)12 * d.ej[k]), Zi = iso_load(d.Zi + (size_t)12 * k);
+    const double* om = d.info + (size_t)36 * k;
+    const Iso E = iso_mul(iso_mul(Zi, iso_inv(Xi)), Xj);
+    const Q4 qe = unit_q(E.R);
+    const double e[6] = {E.t.x, E.t.y, E.t.z, qe.x, qe.y, qe.z};
+    double we[6], chi = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        double t = 0.0;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) t += om[i * 6 + j] * e[j];
+        we[i] = t;
+        chi += e[i] * t;
+    }
+    d.echi[k] = chi;
+    if (!JAC) return;
+    // linearizeOplus: E = Z^-1 (Xi^-1 Xj) = Zi B, q its unit quaternion; derivation next to EdgeSE3::linearizeOplus
+    const Iso B = iso_mul(iso_inv(Xi), Xj), E2 = iso_mul(Zi, B);
+    const Q4 q = unit_q(E2.R);
+    const M3 RZt = Zi.R, V = hat(v3(q.x, q.y, q.z)), TB = hat(B.t), RZtTB = mul(RZt, TB);
+    M3 Qm, Qp;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { const double dg = (i % 4 == 0) ? q.w : 0.0; Qm.a[i] = dg - V.a[i]; Qp.a[i] = dg + V.a[i]; }
+    const M3 QmRZt = mul(Qm, RZt);
+    double J0[36], J1[36];
+#pragma unroll
+    for (int i = 0; i < 36; ++i) { J0[i] = 0.0; J1[i] = 0.0; }
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            J0[r * 6 + c] = -RZt.a[r * 3 + c];
+            J0[r * 6 + 3 + c] = 2.0 * RZtTB.a[r * 3 + c];
+            J0[(3 + r) * 6 + 3 + c] = -QmRZt.a[r * 3 + c];
+            J1[r * 6 + c] = E2.R.a[r * 3 + c];
+            J1[(3 + r) * 6 + 3 + c] = Qp.a[r * 3 + c];
+        }
+    double* rec = d.erec + (size_t)PGO_REC * k;
+    // g_a = J_a^T O e  (b -= g_a in the sum)
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+        double t0 = 0.0, t1 = 0.0;
+#pragma unroll
+        for (int r = 0; r < 6; ++r) { t0 += J0[r * 6 + c] * we[r]; t1 += J1[r * 6 + c] * we[r]; }
+        rec[108 + c] = t0; rec[114 + c] = t1;
+    }
+    // O J0 -> A00 = J0^T (O J0), A10 = J1^T (O J0); then O J1 -> A11
+    double OJ[36];
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) { double t = 0.0;
+#pragma unroll
+            for (int q2 = 0; q2 < 6; ++q2) t += om[r * 6 + q2] * J0[q2 * 6 + c];
+            OJ[r * 6 + c] = t; }
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            double t0 = 0.0, t1 = 0.0;
+#pragma unroll
+            for (int q2 = 0; q2 < 6; ++q2) { t0 += J0[q2 * 6 + r] * OJ[q2 * 6 + c]; t1 += J1[q2 * 6 + r] * OJ[q2 * 6 + c]; }
+            rec[r * 6 + c] = t0; rec[72 + r * 6 + c] = t1;
+        }
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) { double t = 0.0;
+#pragma unroll
+            for (int q2 = 0; q2 < 6; ++q2) t += om[r * 6 + q2] * J1[q2 * 6 + c];
+            OJ[r * 6 + c] = t; }
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            double t = 0.0;
+#pragma unroll
+            for (int q2 = 0; q2 < 6; ++q2) t += J1[q2 * 6 + r] * OJ[q2 * 6 + c];
+            rec[36 + r * 6 + c] = t;
+        }
+}
+
+// Hblk, b: a wave per block, lane l < 36 owns entry l, lanes 36..41 the block's b (diagonal blocks); sources in edge order
+__global__ __launch_bounds__(256) void k_pgo_sum(PgoDev d) {
+    if (d.ctl->done || !d.ctl->lin) return;
+    const int blk = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63;
+    if (blk >= d.nblk || l >= 42) return;
+    if (l >= 36 && !d.blk_diag[blk]) return;
+    const int r = (l < 36) ? l / 6 : l - 36, c = l % 6;
+    double acc = 0.0;
+    for (int s = d.blk_start[blk]; s < d.blk_start[blk + 1]; ++s) {
+        const int src = d.blk_src[s], k = src >> 2, slot = src & 3;
+        const double* rec = d.erec + (size_t)PGO_REC * k;
+        if (l >= 36) acc -= rec[(slot == 0 ? 108 : 114) + r];
+        else if (slot == 3) acc += rec[72 + c * 6 + r];
+        else acc += rec[slot * 36 + r * 6 + c];
+    }
+    if (l < 36) d.Hblk[(size_t)36 * blk + l] = acc;
+    else d.b[6 * d.blk_row[blk] + r] = acc;
+}
+
+// fixed-order sum over one workgroup of 256: thread t takes t, t + 256, ... in order, then a fixed tree
+__device__ double wg_sum(double v, double* sh) {
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    const double r = sh[0];
+    __syncthreads();
+    return r;
+}
+__device__ double chi_total(const PgoDev& d, double* sh) {
+    double v = 0.0;
+    for (int k = threadIdx.x; k < d.ne; k += 256) v += d.echi[k];
+    return wg_sum(v, sh);
+}
+
+// start of an iteration: currentChi = activeRobustChi2 of the linearised state; computeLambdaInit in the first one
+__global__ __launch_bounds__(256) void k_pgo_iter(PgoDev d) {
+    __shared__ double sh[256];
+    if (d.ctl->done || !d.ctl->lin) return;
+    const double chi = chi_total(d, sh);
+    double md = 0.0;
+    if (d.ctl->iters == 0)
+        for (int i = threadIdx.x; i < d.P; i += 256) md = fmax(md, fabs(d.Hblk[(size_t)36 * d.dg_blk[i / 6] + (i % 6) * 7]));
+    sh[threadIdx.x] = md;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] = fmax(sh[threadIdx.x], sh[threadIdx.x + s]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        PgoCtl* g = d.ctl;
+        g->c.current_chi = chi;
+        if (g->iters == 0) {
+            g->chi2_initial = chi;
+            g->c.maxdiag = sh[0];
+            g->c.lambda = d.user_lambda > 0 ? d.user_lambda : d.tau * sh[0];
+            g->c.ni = 2.0;
+        }
+        g->c.trial = 0;
+        g->lin = 0;
+    }
+}
+
+// sys = H + lambda I over the whole (Ppad + 64) x ld image (the factorisation works in place, so every trial writes all of it)
+__global__ __launch_bounds__(256) void k_pgo_fill(PgoDev d) {
+    const int c = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y;
+    if (c >= d.ld) return;
+    const bool done = d.ctl->done != 0;
+    if (r == 0 && c == 0) d.ctl->c.solver_ok = 1;
+    double v = 0.0;
+    if (done) v = (r < d.Ppad && r == c) ? 1.0 : 0.0;      // the run has ended: the (ungated) factorisation behind gets the identity
+    else if (r < d.P) {
+        if (c < d.P) {
+            const int id = d.blkmap[(size_t)(r / 6) * d.n + c / 6];
+            if (id >= 0) v = d.Hblk[(size_t)36 * (id >> 1) + ((id & 1) ? (c % 6) * 6 + r % 6 : (r % 6) * 6 + c % 6)];
+            if (r == c) v += d.ctl->c.lambda;
+        }
+    } else if (r < d.Ppad) v = (r == c) ? 1.0 : 0.0;
+    else if (r == d.Ppad) v = (c < d.P) ? d.b[c] : 0.0;
+    d.sys[(size_t)r * d.ld + c] = v;
+}
+
+// push + oplus of the free vertices (VertexSE3::oplusImpl, the counter counts every call, rejected trials included)
+__global__ __launch_bounds__(64) void k_pgo_update(PgoDev d) {
+    if (d.ctl->done) return;
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    if (k >= d.n) return;
+    const int v = d.free_v[k];
+    double* xp = d.X + (size_t)12 * v;
+    double* sp = d.Xs + (size_t)12 * v;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) sp[i] = xp[i];
+    double u[6];
+    const bool ok = d.ctl->c.solver_ok != 0;      // a failed factorisation: the host path's x = 0
+#pragma unroll
+    for (int i = 0; i < 6; ++i) u[i] = ok ? d.x[6 * k + i] : 0.0;
+    Iso X = iso_mul(iso_load(xp), iso_from_mqt(u));
+    if (++d.cnt[v] > ORTHO_AFTER) {      // approximateNearestOrthogonalMatrix: R -= 0.5 R (R^T R - I)
+        d.cnt[v] = 0;
+        M3 E = mulAtB(X.R, X.R);
+        E.a[0] -= 1; E.a[4] -= 1; E.a[8] -= 1;
+        const M3 RE = mul(X.R, E);
+#pragma unroll
+        for (int i = 0; i < 9; ++i) X.R.a[i] -= 0.5 * RE.a[i];
+    }
+    iso_store(X, xp);
+}
+
+__device__ void pgo_deliver(const PgoDev& d, unsigned long long seq) {
+    d.mail->h.done = d.ctl->done; d.mail->h.iters = d.ctl->iters; d.mail->h.trials = d.ctl->trials;
+    __threadfence_system();
+    __hip_atomic_store(&d.mail->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// end of a trial: the Levenberg branch of optimizeHost, then the loop exits
+__global__ __launch_bounds__(256) void k_pgo_decide(PgoDev d, unsigned long long seq) {
+    __shared__ double sh[256];
+    __shared__ int s_reject;
+    PgoCtl* g = d.ctl;
+    if (g->done) { if (threadIdx.x == 0) pgo_deliver(d, seq); return; }
+    const double lambda = g->c.lambda;
+    const bool ok = g->c.solver_ok != 0;
+    const double chi = chi_total(d, sh);
+    double sp = 0.0;
+    if (ok) for (int j = threadIdx.x; j < d.P; j += 256) sp += d.x[j] * (lambda * d.x[j] + d.b[j]);
+    sp = wg_sum(sp, sh);
+    if (threadIdx.x == 0) {
+        double tempChi = chi;
+        if (!ok) tempChi = 1.7976931348623157e308;      // DBL_MAX
+        const double scale = 1e-3 + sp;
+        const double rho = (g->c.current_chi - tempChi) / scale;
+        const bool acc = rho > 0 && isfinite(tempChi);
+        plba_trace_row row;
+        row.iteration = g->iters; row.trial = g->c.trial; row.accepted = acc ? 1 : 0; row.solver_ok = ok ? 1 : 0;
+        row.lambda = lambda; row.chi2_current = g->c.current_chi; row.chi2_trial = tempChi; row.scale = scale; row.rho = rho;
+        if (g->n_trace < d.trace_cap) d.trace[g->n_trace] = row;
+        g->n_trace += 1;
+        g->trials += 1;
+        if (!ok) g->c.n_fail += 1;
+        g->c.temp_chi = tempChi; g->c.scale = scale; g->c.rho = rho; g->c.accepted = acc ? 1 : 0;
+        bool brk = false;
+        if (acc) {
+            double alpha = 1.0 - pow(2 * rho - 1, 3);
+            alpha = fmin(alpha, d.upper);
+            g->c.lambda = lambda * fmax(d.lower, alpha);
+            g->c.ni = 2.0;
+            g->c.current_chi = tempChi;
+        } else {
+            g->c.lambda = lambda * g->c.ni;
+            g->c.ni *= 2.0;
+            brk = !isfinite(g->c.lambda);
+        }
+        s_reject = acc ? 0 : 1;
+        int qmax = g->c.trial;
+        if (!brk) ++qmax;
+        g->c.trial = qmax;
+        if (brk || !(rho < 0 && qmax < d.max_trials)) {      // the iteration ends
+            g->iters += 1;
+            g->chi2_final = g->c.current_chi; g->lambda_final = g->c.lambda;
+            if (qmax == d.max_trials || rho == 0 || !isfinite(g->c.lambda)) { g->stop_reason = 1; g->done = 1; }
+            else if (g->iters >= d.max_iters) g->done = 1;
+            else g->lin = 1;
+        }
+    }
+    __syncthreads();
+    if (s_reject)      // pop
+        for (int i = threadIdx.x; i < 12 * d.n; i += 256) { const size_t o = (size_t)12 * d.free_v[i / 12] + i % 12; d.X[o] = d.Xs[o]; }
+    if (threadIdx.x == 0) pgo_deliver(d, seq);
+}
+
+// max_iters = 0 or nothing to optimise: chi2 only
+__global__ __launch_bounds__(256) void k_pgo_chi_only(PgoDev d) {
+    __shared__ double sh[256];
+    const double chi = chi_total(d, sh);
+    if (threadIdx.x == 0) { d.ctl->chi2_initial = chi; d.ctl->chi2_final = chi; }
+}
+
+struct HIso { double R[9], t[3]; };
+HIso h_load(const double* p) { HIso a; memcpy(a.R, p, 72); memcpy(a.t, p + 9, 24); return a; }
+void h_store(const HIso& a, double* p) { memcpy(p, a.R, 72); memcpy(p + 9, a.t, 24); }
+// slam3d_detail::mul / inv on the host (same products as plba::mul, no contraction into FMAs on the host)
+HIso h_mul(const HIso& a, const HIso& b) {
+    M3 A, Bm; memcpy(A.a, a.R, 72); memcpy(Bm.a, b.R, 72);
+    const M3 R = mul(A, Bm);
+    const V3 t = mul(A, v3(b.t[0], b.t[1], b.t[2])) + v3(a.t[0], a.t[1], a.t[2]);
+    HIso r; memcpy(r.R, R.a, 72); r.t[0] = t.x; r.t[1] = t.y; r.t[2] = t.z;
+    return r;
+}
+HIso h_inv(const HIso& a) {
+    M3 A; memcpy(A.a, a.R, 72);
+    const M3 Rt = transpose(A);
+    const V3 x = mul(Rt, v3(a.t[0], a.t[1], a.t[2]));
+    HIso r; memcpy(r.R, Rt.a, 72); r.t[0] = -x.x; r.t[1] = -x.y; r.t[2] = -x.z;
+    return r;
+}
+
+}  // namespace
+}  // namespace plba
+
+using namespace plba;
+
+extern "C" {
+
+int plba_optimize_pose_graph(plba_problem* p, plba_pose_graph* g, int max_iters, double user_lambda_init, int initial_guess,
+                             plba_stats* out, plba_trace_row* trace, int trace_cap, int* n_trace) {
+    if (!p) return PLBA_ERR_INVALID;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!g || !out) FAIL(p, PLBA_ERR_INVALID, "plba_optimize_pose_graph: no graph or no stats");
+    if (trace_cap < 0 || (trace_cap > 0 && !trace)) FAIL(p, PLBA_ERR_INVALID, "plba_optimize_pose_graph: trace_cap > 0 without a trace");
+    if (max_iters < 0) FAIL(p, PLBA_ERR_INVALID, "plba_optimize_pose_graph: max_iters < 0");
+    if (!std::isfinite(user_lambda_init)) FAIL(p, PLBA_ERR_INVALID, "plba_optimize_pose_graph: user_lambda_init is not finite");
+    const int nv = g->nv, ne = g->ne;
+    if (nv <= 0 || ne < 0) FAIL(p, PLBA_ERR_INVALID, "plba_optimize_pose_graph: nv = %d, ne = %d", nv, ne);
+    if (!g->pose12 || (ne > 0 && (!g->ei || !g->ej || !g->meas12))) FAIL(p, PLBA_ERR_INVALID, "plba_optimize_pose_graph: missing array");
+    for (size_t i = 0; i < (size_t)12 * nv; ++i)
+        if (!std::isfinite(g->pose12[i])) FAIL(p, PLBA_ERR_INVALID, "plba_optimize_pose_graph: pose of vertex %d is not finite", (int)(i / 12));
+    for (int k = 0; k < ne; ++k) {
+        if (g->ei[k] < 0 || g->ei[k] >= nv || g->ej[k] < 0 || g->ej[k] >= nv) FAIL(p, PLBA_ERR_INVALID, "plba_optimize_pose_graph: edge %d names a vertex out of range", k);
+        if (g->ei[k] == g->ej[k]) FAIL(p, PLBA_ERR_INVALID, "plba_optimize_pose_graph: edge %d joins vertex %d to itself", k, g->ei[k]);
+        for (int i = 0; i < 12; ++i) if (!std::isfinite(g->meas12[(size_t)12 * k + i])) FAIL(p, PLBA_ERR_INVALID, "plba_optimize_pose_graph: measurement of edge %d is not finite", k);
+        if (g->info36) for (int i = 0; i < 36; ++i) if (!std::isfinite(g->info36[(size_t)36 * k + i])) FAIL(p, PLBA_ERR_INVALID, "plba_optimize_pose_graph: information of edge %d is not finite", k);
+    }
+    auto is_fixed = [&](int v) { return g->fixed && g->fixed[v] != 0; };
+
+    // ---- host: estimates, initial guess, active set, block structure --------------------------------------------------------------
+    std::vector<double> X(g->pose12, g->pose12 + (size_t)12 * nv);
+    if (initial_guess && ne > 0) {
+        // the facade's computeInitialGuess (g2o_compat.h): frontier = fixed vertices in the order the edges name them; each `from` of a
+        // frontier scans its edges in insertion order: to = from Z (from is vertex 0) or from Z^-1; O(V + E) with incident-edge lists
+        std::vector<int32_t> inc_start(nv + 1, 0), inc((size_t)2 * ne);
+        for (int k = 0; k < ne; ++k) { ++inc_start[g->ei[k] + 1]; ++inc_start[g->ej[k] + 1]; }
+        for (int v = 0; v < nv; ++v) inc_start[v + 1] += inc_start[v];
+        { std::vector<int32_t> cur(inc_start.begin(), inc_start.end() - 1); for (int k = 0; k < ne; ++k) { inc[cur[g->ei[k]]++] = k; inc[cur[g->ej[k]]++] = k; } }
+        std::vector<char> done(nv, 0);
+        std::vector<int> front, next;
+        for (int k = 0; k < ne; ++k) for (int v : {g->ei[k], g->ej[k]}) if (is_fixed(v) && !done[v]) { done[v] = 1; front.push_back(v); }
+        while (!front.empty()) {
+            next.clear();
+            for (int from : front)
+                for (int q = inc_start[from]; q < inc_start[from + 1]; ++q) {
+                    const int k = inc[q];
+                    const int to = g->ei[k] == from ? g->ej[k] : g->ei[k];
+                    if (done[to] || is_fixed(to)) continue;
+                    const HIso Z = h_load(g->meas12 + (size_t)12 * k);
+                    h_store(h_mul(h_load(&X[(size_t)12 * from]), g->ei[k] == from ? Z : h_inv(Z)), &X[(size_t)12 * to]);
+                    done[to] = 1; next.push_back(to);
+                }
+            front.swap(next);
+        }
+    }
+    std::vector<int32_t> fr(nv, -1), free_v;
+    {
+        std::vector<char> touched(nv, 0);
+        for (int k = 0; k < ne; ++k) { touched[g->ei[k]] = 1; touched[g->ej[k]] = 1; }
+        for (int v = 0; v < nv; ++v) if (touched[v] && !is_fixed(v)) { fr[v] = (int32_t)free_v.size(); free_v.push_back(v); }
+    }
+    const int n = (int)free_v.size(), P = 6 * n;
+    const bool run = max_iters > 0 && n > 0;
+    std::vector<int32_t> blk_start, blk_src, blk_diag, blk_row, dg_blk, blkmap;
+    if (run) {
+        struct Src { int32_t r, c, src; };
+        std::vector<Src> s;
+        s.reserve((size_t)3 * ne);
+        for (int k = 0; k < ne; ++k) {
+            const int a = fr[g->ei[k]], b = fr[g->ej[k]];
+            if (a >= 0) s.push_back({a, a, 4 * k + 0});
+            if (b >= 0) s.push_back({b, b, 4 * k + 1});
+            if (a >= 0 && b >= 0) { if (b > a) s.push_back({b, a, 4 * k + 2}); else s.push_back({a, b, 4 * k + 3}); }
+        }
+        std::stable_sort(s.begin(), s.end(), [](const Src& x, const Src& y) { return x.r != y.r ? x.r < y.r : x.c < y.c; });   // edge order within a block
+        blkmap.assign((size_t)n * n, -1);
+        dg_blk.assign(n, -1);
+        for (size_t i = 0; i < s.size(); ++i) {
+            if (i == 0 || s[i].r != s[i - 1].r || s[i].c != s[i - 1].c) {
+                const int id = (int)blk_row.size();
+                blk_start.push_back((int32_t)i); blk_row.push_back(s[i].r); blk_diag.push_back(s[i].r == s[i].c ? 1 : 0);
+                blkmap[(size_t)s[i].r * n + s[i].c] = 2 * id;
+                if (s[i].r != s[i].c) blkmap[(size_t)s[i].c * n + s[i].r] = 2 * id + 1;
+                else dg_blk[s[i].r] = id;
+            }
+            blk_src.push_back(s[i].src);
+        }
+        blk_start.push_back((int32_t)s.size());
+    }
+    const int nblk = (int)blk_row.size();
+
+    // ---- device ------------------------------------------------------------------------------------------------------------------
+    HIPCK(p, hipSetDevice(p->device));
+    hipStream_t s = p->stream;
+    const int Ppad = std::max(TILE, (P + TILE - 1) / TILE * TILE), ld = Ppad;
+    const size_t sysn = run ? (size_t)(Ppad + TILE) * ld : 1;
+    std::vector<double> Zi((size_t)12 * std::max(ne, 1), 0.0), info((size_t)36 * std::max(ne, 1), 0.0);
+    for (int k = 0; k < ne; ++k) {
+        h_store(h_inv(h_load(g->meas12 + (size_t)12 * k)), &Zi[(size_t)12 * k]);
+        if (g->info36) memcpy(&info[(size_t)36 * k], g->info36 + (size_t)36 * k, 36 * 8);
+        else for (int i = 0; i < 6; ++i) info[(size_t)36 * k + 7 * i] = 1.0;
+    }
+    std::vector<int32_t> hei(g->ei ? g->ei : nullptr, g->ei ? g->ei + ne : nullptr), hej(g->ej ? g->ej : nullptr, g->ej ? g->ej + ne : nullptr);
+    if (hei.empty()) { hei.assign(1, 0); hej.assign(1, 0); }
+    if (free_v.empty()) free_v.assign(1, 0);
+    auto nz = [](std::vector<int32_t>& v) { if (v.empty()) v.assign(1, 0); };
+    nz(blk_start); nz(blk_src); nz(blk_diag); nz(blk_row); nz(dg_blk); nz(blkmap);
+    DArr<double> dX, dXs, dZi, dInfo, dErec, dEchi, dHblk, db, sys, Lfac, xx, Linv, LT32, rd32, Ninv;
+    DArr<int32_t> dfree, dei, dej, dbs, dbsrc, dbdiag, dbrow, ddg, dmap;
+    DArr<int> dcnt, flags, cflags;
+    DArr<PgoCtl> dctl;
+    DArr<plba_trace_row> dtrace;
+    PgoCtl c0; memset(&c0, 0, sizeof c0);
+    c0.lin = 1; c0.c.solver_ok = 1;
+    std::vector<PgoCtl> hc0(1, c0);
+    {
+        DArrStreamScope staged(s, p->have_ctx ? p->ctx.stage : nullptr);      // host vectors above stay alive until the wait below
+        HIPCK(p, dX.upload(X)); HIPCK(p, dXs.alloc((size_t)12 * nv)); HIPCK(p, dcnt.alloc(nv));
+        HIPCK(p, dZi.upload(Zi)); HIPCK(p, dInfo.upload(info)); HIPCK(p, dei.upload(hei)); HIPCK(p, dej.upload(hej));
+        HIPCK(p, dEchi.alloc(std::max(ne, 1))); HIPCK(p, dctl.upload(hc0)); HIPCK(p, dtrace.alloc(std::max(trace_cap, 1)));
+        if (run) {
+            HIPCK(p, dfree.upload(free_v)); HIPCK(p, dbs.upload(blk_start)); HIPCK(p, dbsrc.upload(blk_src));
+            HIPCK(p, dbdiag.upload(blk_diag)); HIPCK(p, dbrow.upload(blk_row)); HIPCK(p, ddg.upload(dg_blk)); HIPCK(p, dmap.upload(blkmap));
+            HIPCK(p, dErec.alloc((size_t)PGO_REC * std::max(ne, 1))); HIPCK(p, dHblk.alloc((size_t)36 * std::max(nblk, 1))); HIPCK(p, db.alloc(P));
+            HIPCK(p, sys.alloc(sysn, false)); HIPCK(p, Lfac.alloc(sysn)); HIPCK(p, xx.alloc(ld));
+            HIPCK(p, Linv.alloc((size_t)(Ppad / TILE) * TILE * TILE)); HIPCK(p, flags.alloc(Ppad / TILE)); HIPCK(p, LT32.alloc((size_t)Ppad * 64)); HIPCK(p, rd32.alloc(Ppad));
+            HIPCK(p, cflags.alloc((size_t)(Ppad / 32 + 2) * (Ppad / 32)));
+            if (Ppad / 32 <= NINV_MAX_T) HIPCK(p, Ninv.alloc((size_t)2 * Ppad * ld));
+        }
+        HIPCK(p, plba_stream_wait(p, s));
+    }
+    PgoDev d; memset(&d, 0, sizeof d);
+    d.nv = nv; d.ne = ne; d.n = n; d.P = P; d.Ppad = Ppad; d.ld = ld; d.nblk = nblk; d.max_iters = max_iters; d.max_trials = p->opt.max_trials; d.trace_cap = trace_cap;
+    d.tau = p->opt.tau; d.lower = p->opt.good_step_lower; d.upper = p->opt.good_step_upper; d.user_lambda = user_lambda_init;
+    d.X = dX.p; d.Xs = dXs.p; d.cnt = dcnt.p; d.free_v = dfree.p; d.ei = dei.p; d.ej = dej.p; d.Zi = dZi.p; d.info = dInfo.p;
+    d.erec = dErec.p; d.echi = dEchi.p; d.blk_start = dbs.p; d.blk_src = dbsrc.p; d.blk_diag = dbdiag.p; d.blk_row = dbrow.p; d.dg_blk = ddg.p; d.blkmap = dmap.p;
+    d.Hblk = dHblk.p; d.b = db.p; d.sys = sys.p; d.x = xx.p; d.ctl = dctl.p; d.mail = reinterpret_cast<PgoMail*>(p->d_mail); d.trace = dtrace.p;
+    DevBuf dd; memset(&dd, 0, sizeof dd);
+    dd.P = P; dd.Ppad = Ppad; dd.ld = ld; dd.sys = sys.p; dd.Lfac = Lfac.p; dd.x = xx.p; dd.ctrl = &dctl.p->c; dd.Linv = Linv.p; dd.flow_flags = flags.p; dd.LTblk = LT32.p; dd.Linv32 = LT32.p; dd.rdblk = rd32.p;
+    dd.fb = (p->opt.factor_block == 64) ? 64 : 32; dd.chol_flags = cflags.p; dd.flow = p->opt.factor_flow != 0; dd.wide = p->opt.wide_steps != 0 && !dd.flow;
+    if (Ninv.p) { dd.Ninv = Ninv.p; dd.Nwork = Ninv.p + (size_t)Ppad * ld; }
+
+    const dim3 eg((unsigned)((std::max(ne, 1) + 63) / 64)), vg((unsigned)((n + 63) / 64)), bg((unsigned)((std::max(nblk, 1) + 3) / 4)), fg((unsigned)((ld + 255) / 256), (unsigned)(Ppad + TILE));
+    if (!run) {
+        if (ne > 0) hipLaunchKernelGGL(k_pgo_edges<false>, eg, dim3(64), 0, s, d);
+        hipLaunchKernelGGL(k_pgo_chi_only, dim3(1), dim3(256), 0, s, d);
+    } else {
+        const int max_steps = max_iters * std::max(p->opt.max_trials, 1);
+        volatile PgoMail* hm = reinterpret_cast<volatile PgoMail*>(p->h_mail);
+        const unsigned long long seq0 = p->mail_seq;      // sequence numbers go on from the problem's: never one the mailbox has held before
+        p->mail_seq += (unsigned long long)max_steps + 1;
+        for (int step = 0; step < max_steps; ++step) {
+            const unsigned long long seq = seq0 + (unsigned long long)step + 1;
+            hipLaunchKernelGGL(k_pgo_edges<true>, eg, dim3(64), 0, s, d);
+            hipLaunchKernelGGL(k_pgo_sum, bg, dim3(256), 0, s, d);
+            hipLaunchKernelGGL(k_pgo_iter, dim3(1), dim3(256), 0, s, d);
+            hipLaunchKernelGGL(k_pgo_fill, fg, dim3(256), 0, s, d);
+            launch_cholesky(dd, p->opt.use_mfma != 0, step + 1, s);      // (not gated: after the run has ended it factors the identity, at most one step of it)
+            launch_trsv_back(dd, p->opt.use_mfma != 0, step + 1, s);
+            hipLaunchKernelGGL(k_pgo_update, vg, dim3(64), 0, s, d);
+            hipLaunchKernelGGL(k_pgo_edges<false>, eg, dim3(64), 0, s, d);
+            hipLaunchKernelGGL(k_pgo_decide, dim3(1), dim3(256), 0, s, d, seq);
+            HIPCK(p, hipGetLastError());
+            if (step > 0) {      // one step behind: has step - 1 ended the run?  (this step is in the queue already)
+                const unsigned long long want = seq - 1;
+                long spins = 0;
+                while (__atomic_load_n(const_cast<const unsigned long long*>(&hm->seq), __ATOMIC_ACQUIRE) < want) {      // (what the mailbox held before is <= seq0)
+                    if (++spins > (1L << 22)) { HIPCK(p, plba_stream_wait(p, s)); break; }
+                }
+                if (hm->h.done) break;
+            }
+        }
+    }
+    HIPCK(p, plba_stream_wait(p, s));
+    HIPCK(p, hipGetLastError());
+    PgoCtl cend;
+    HIPCK(p, plba_d2h(p, X.data(), dX.p, (size_t)12 * nv * 8));
+    HIPCK(p, plba_d2h(p, &cend, dctl.p, sizeof cend));
+    const int nrow = std::min(cend.n_trace, trace_cap);
+    if (nrow > 0) HIPCK(p, plba_d2h(p, trace, dtrace.p, (size_t)nrow * sizeof(plba_trace_row)));
+    memcpy(g->pose12, X.data(), (size_t)12 * nv * 8);
+    memset(out, 0, sizeof *out);
+    out->iterations = cend.iters; out->trials = cend.trials; out->stop_reason = cend.stop_reason; out->solver_failures = cend.c.n_fail;
+    out->chi2_initial = cend.chi2_initial; out->chi2_final = cend.chi2_final; out->lambda_final = cend.lambda_final;
+    out->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (n_trace) *n_trace = cend.n_trace;
+    return PLBA_OK;
+}
+
+}  // extern "C"
