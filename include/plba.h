@@ -116,6 +116,9 @@ typedef struct {
                                    bit 2 (fault injection, tests/test_lm_fused.py): the in-launch wait of k_lm_trial is given a count that
                                    never comes — the call must fail with PLBA_ERR_DEVICE, not hang; bit 3 (measurement / tests): the
                                    Jacobi of the marginalization's kept block starts cold, without the tridiagonal pre-rotation    (0) */
+    int    pgo_solver;          /* linear solver of plba_optimize_pose_graph: 0 = dense Cholesky of the whole system; 1 = sparse
+                                   multifrontal Cholesky (nested dissection, 6 x 6 blocks), for whole-map graphs; any other value:
+                                   plba_optimize_pose_graph fails with PLBA_ERR_INVALID                                      (0) */
 } plba_options;
 #define PLBA_DIAG_TIMING 1
 #define PLBA_DIAG_MARG_DUMP 2
@@ -441,7 +444,15 @@ int plba_lba_visual(plba_problem* p, const plba_lba_options* opt, int K, const d
  * user_lambda_init: g2o's userLambdaInit (the reference: 1e-10); 0 = options.tau * max diag(H).  The LM constants tau,
  * max_trials and the good-step bounds come from the problem's options.  max_iters = 0 only evaluates chi2.
  * Refused with PLBA_ERR_INVALID and pose12 untouched: nv <= 0, an index out of range, ei == ej, a non-finite input, a missing
- * array or output.  The problem's uploaded window is neither read nor written. */
+ * array or output, options.pgo_solver not 0 or 1.  The problem's uploaded window is neither read nor written.
+ * Linear solver (options.pgo_solver): 0 = the dense fp64 Cholesky of the whole (6 x free vertices)^2 system, O(P^2) memory and
+ * O(P^3) time per trial; 1 = a sparse multifrontal Cholesky: a nested-dissection ordering of the free-vertex graph and the
+ * symbolic factorisation on 6 x 6 blocks are built once per call on the host, then every trial assembles H + lambda I into the
+ * fronts, factors them level by level up the elimination tree and back-substitutes down it, all on the device; memory grows with
+ * the fill of L.  Same LM loop, same failure semantics (a pivot <= 0: solver_ok = 0, x = 0), bit-reproducible; the two paths
+ * agree to rounding.  plba_debug_get(p, "pgo_sparse") (8, at any time) describes the last call: [0] 1 if it took the sparse path,
+ * [1] free vertices, [2] fronts, [3] tree levels, [4] nonzero 6 x 6 blocks of L, [5] largest front dimension, [6] device bytes
+ * the call allocated, [7] host ms of the analysis ([1..7] 0 when there was nothing to solve); all 0 before the first call and after a refused one. */
 typedef struct plba_pose_graph {
     int            nv;          /* vertices                                                                           */
     double*        pose12;      /* in/out [nv][12]: R row-major (9), t (3) of each VertexSE3 estimate (Isometry3)      */
@@ -465,7 +476,8 @@ int plba_optimize_pose_graph(plba_problem* p, plba_pose_graph* g, int max_iters,
  * "bl_ln" (Nl*6), "err_pvr" (M*9), "err_bias" (M*6), "err_prior" (n), "pose_dim" (1), "chi2" (1),
  * "maxdiag" (1); "marg_path" (5, after plba_marginalize*): [0] 0 = block-wise pseudo-inverse taken, 1 = dense
  * eigen-decomposition of Amm; [1..4] the certificate's w_max, smallest kept landmark eigenvalue, tau, smallest pivot;
- * "host_waits" (1, at any time, waits for nothing): how often the library has blocked the calling thread on the device. */
+ * "host_waits" (1, at any time, waits for nothing): how often the library has blocked the calling thread on the device;
+ * "pgo_sparse" (8, at any time): the last plba_optimize_pose_graph's solver (see there). */
 int plba_debug_build(plba_problem* p, double lambda, int do_solve);
 int plba_debug_get(plba_problem* p, const char* what, double* out, size_t cap, size_t* n);
 /* the same entry under its round-1 name (tests/test_gpu_parity.py); product code calls plba_dense_solve */

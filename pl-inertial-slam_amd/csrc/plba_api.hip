@@ -57,6 +57,7 @@ static void reset_for_reuse(plba_problem* p, const plba_options* opt) {
     p->level.clear(); p->imu_i.clear(); p->imu_j.clear(); p->imu_pre.clear(); p->imu_ipvr.clear(); p->imu_ibias.clear();
     p->pr_n = p->pr_nv = 0; p->pr_vid.clear(); p->pr_size.clear(); p->pr_idx.clear(); p->pr_x0.clear(); p->pr_J0.clear(); p->pr_r0.clear();
     p->prior_dev = false; p->prior_changed = false; p->pr_m = 0; p->host_waits = 0;
+    for (double& v : p->pgo_sparse) v = 0.0;
     memset(&p->rob, 0, sizeof p->rob);
     p->rank = 0; p->world = 1; p->xfn = nullptr; p->xuser = nullptr;
     p->dirty = true; p->P = p->Ppad = p->ld = p->L = p->E = 0; p->cur = 0;
@@ -2970,6 +2971,11 @@ int plba_debug_get(plba_problem* p, const char* what, double* out, size_t cap, s
     if (w == "host_waits") {      // (read without waiting for anything)
         if (n) *n = 1;
         if (out && cap) *out = (double)p->host_waits;
+        return PLBA_OK;
+    }
+    if (w == "pgo_sparse") {      // (host-side record of the last plba_optimize_pose_graph: the pose graph uploads no window)
+        if (n) *n = 8;
+        for (size_t i = 0; out && i < cap && i < 8; ++i) out[i] = p->pgo_sparse[i];
         return PLBA_OK;
     }
     if (p->dirty) FAIL(p, PLBA_ERR_STATE, "debug_get before debug_build/optimize");

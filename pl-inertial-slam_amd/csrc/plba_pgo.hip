@@ -21,6 +21,8 @@
 //   k_pgo_update          backup, X <- X fromVectorMQT(x) (x = 0 after a failed factorisation), orthogonalizeAfter
 //   k_pgo_edges<errors>   the trial's chi2 per edge
 //   k_pgo_decide          tempChi, scale, rho, the g2o lambda schedule, restore on rejection, trace row, loop exits, mailbox
+// options.pgo_solver = 1 replaces k_pgo_fill + launch_cholesky + launch_trsv_back by the multifrontal solve of plba_pgo_sparse.h
+// (no blkmap and no dense image; the structure is analysed once per call on the host).
 // Every kernel but the factorisation returns at once after the run has ended (PgoCtl::done).  Nothing of O(P^2) or O(E)
 // crosses PCIe between the upload and the read-back of the poses, the control block and the trace.
 // Bit-reproducible: no floating-point atomics; every sum has one owner and a fixed order.
@@ -32,6 +34,7 @@
 #include <vector>
 
 #include "plba_internal.h"
+#include "plba_pgo_sparse.h"
 #include "plba_problem.h"
 
 #define HIPCK(p, call) PLBA_HIPCK(p, call)
@@ -415,9 +418,11 @@ int plba_optimize_pose_graph(plba_problem* p, plba_pose_graph* g, int max_iters,
                              plba_stats* out, plba_trace_row* trace, int trace_cap, int* n_trace) {
     if (!p) return PLBA_ERR_INVALID;
     const auto t0 = std::chrono::steady_clock::now();
+    for (double& v : p->pgo_sparse) v = 0.0;      // (a refused call leaves an all-zero record)
     if (!g || !out) FAIL(p, PLBA_ERR_INVALID, "plba_optimize_pose_graph: no graph or no stats");
     if (trace_cap < 0 || (trace_cap > 0 && !trace)) FAIL(p, PLBA_ERR_INVALID, "plba_optimize_pose_graph: trace_cap > 0 without a trace");
     if (max_iters < 0) FAIL(p, PLBA_ERR_INVALID, "plba_optimize_pose_graph: max_iters < 0");
+    if (p->opt.pgo_solver != 0 && p->opt.pgo_solver != 1) FAIL(p, PLBA_ERR_INVALID, "plba_optimize_pose_graph: options.pgo_solver = %d", p->opt.pgo_solver);
     if (!std::isfinite(user_lambda_init)) FAIL(p, PLBA_ERR_INVALID, "plba_optimize_pose_graph: user_lambda_init is not finite");
     const int nv = g->nv, ne = g->ne;
     if (nv <= 0 || ne < 0) FAIL(p, PLBA_ERR_INVALID, "plba_optimize_pose_graph: nv = %d, ne = %d", nv, ne);
@@ -465,8 +470,8 @@ int plba_optimize_pose_graph(plba_problem* p, plba_pose_graph* g, int max_iters,
         for (int v = 0; v < nv; ++v) if (touched[v] && !is_fixed(v)) { fr[v] = (int32_t)free_v.size(); free_v.push_back(v); }
     }
     const int n = (int)free_v.size(), P = 6 * n;
-    const bool run = max_iters > 0 && n > 0;
-    std::vector<int32_t> blk_start, blk_src, blk_diag, blk_row, dg_blk, blkmap;
+    const bool run = max_iters > 0 && n > 0, sparse = p->opt.pgo_solver == 1;
+    std::vector<int32_t> blk_start, blk_src, blk_diag, blk_row, blk_col, dg_blk, blkmap;
     if (run) {
         struct Src { int32_t r, c, src; };
         std::vector<Src> s;
@@ -478,27 +483,39 @@ int plba_optimize_pose_graph(plba_problem* p, plba_pose_graph* g, int max_iters,
             if (a >= 0 && b >= 0) { if (b > a) s.push_back({b, a, 4 * k + 2}); else s.push_back({a, b, 4 * k + 3}); }
         }
         std::stable_sort(s.begin(), s.end(), [](const Src& x, const Src& y) { return x.r != y.r ? x.r < y.r : x.c < y.c; });   // edge order within a block
-        blkmap.assign((size_t)n * n, -1);
+        if (!sparse) blkmap.assign((size_t)n * n, -1);
         dg_blk.assign(n, -1);
         for (size_t i = 0; i < s.size(); ++i) {
             if (i == 0 || s[i].r != s[i - 1].r || s[i].c != s[i - 1].c) {
                 const int id = (int)blk_row.size();
-                blk_start.push_back((int32_t)i); blk_row.push_back(s[i].r); blk_diag.push_back(s[i].r == s[i].c ? 1 : 0);
-                blkmap[(size_t)s[i].r * n + s[i].c] = 2 * id;
-                if (s[i].r != s[i].c) blkmap[(size_t)s[i].c * n + s[i].r] = 2 * id + 1;
-                else dg_blk[s[i].r] = id;
+                blk_start.push_back((int32_t)i); blk_row.push_back(s[i].r); blk_col.push_back(s[i].c); blk_diag.push_back(s[i].r == s[i].c ? 1 : 0);
+                if (!sparse) {
+                    blkmap[(size_t)s[i].r * n + s[i].c] = 2 * id;
+                    if (s[i].r != s[i].c) blkmap[(size_t)s[i].c * n + s[i].r] = 2 * id + 1;
+                }
+                if (s[i].r == s[i].c) dg_blk[s[i].r] = id;
             }
             blk_src.push_back(s[i].src);
         }
         blk_start.push_back((int32_t)s.size());
     }
     const int nblk = (int)blk_row.size();
+    PgoSparsePlan plan;
+    if (sparse) {
+        p->pgo_sparse[0] = 1.0;
+        if (run) {
+            const auto ta = std::chrono::steady_clock::now();
+            if (!pgo_sparse_analyse(n, blk_row, blk_col, plan)) FAIL(p, PLBA_ERR_INVALID, "plba_optimize_pose_graph: the sparse analysis failed its checks");
+            p->pgo_sparse[1] = n; p->pgo_sparse[2] = plan.nfront; p->pgo_sparse[3] = plan.nlev; p->pgo_sparse[4] = (double)plan.nnz_blk; p->pgo_sparse[5] = plan.max_m;
+            p->pgo_sparse[7] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ta).count();
+        }
+    }
 
     // ---- device ------------------------------------------------------------------------------------------------------------------
     HIPCK(p, hipSetDevice(p->device));
     hipStream_t s = p->stream;
     const int Ppad = std::max(TILE, (P + TILE - 1) / TILE * TILE), ld = Ppad;
-    const size_t sysn = run ? (size_t)(Ppad + TILE) * ld : 1;
+    const size_t sysn = run && !sparse ? (size_t)(Ppad + TILE) * ld : 1;
     std::vector<double> Zi((size_t)12 * std::max(ne, 1), 0.0), info((size_t)36 * std::max(ne, 1), 0.0);
     for (int k = 0; k < ne; ++k) {
         h_store(h_inv(h_load(g->meas12 + (size_t)12 * k)), &Zi[(size_t)12 * k]);
@@ -513,6 +530,9 @@ int plba_optimize_pose_graph(plba_problem* p, plba_pose_graph* g, int max_iters,
     DArr<double> dX, dXs, dZi, dInfo, dErec, dEchi, dHblk, db, sys, Lfac, xx, Linv, LT32, rd32, Ninv;
     DArr<int32_t> dfree, dei, dej, dbs, dbsrc, dbdiag, dbrow, ddg, dmap;
     DArr<int> dcnt, flags, cflags;
+    DArr<int32_t> sp_m, sp_np, sp_row0, sp_rows, sp_umap, sp_chs, sp_ch, sp_ass, sp_as, sp_lv;
+    DArr<long long> sp_off, sp_roff;
+    DArr<double> sp_F, sp_R;
     DArr<PgoCtl> dctl;
     DArr<plba_trace_row> dtrace;
     PgoCtl c0; memset(&c0, 0, sizeof c0);
@@ -525,12 +545,22 @@ int plba_optimize_pose_graph(plba_problem* p, plba_pose_graph* g, int max_iters,
         HIPCK(p, dEchi.alloc(std::max(ne, 1))); HIPCK(p, dctl.upload(hc0)); HIPCK(p, dtrace.alloc(std::max(trace_cap, 1)));
         if (run) {
             HIPCK(p, dfree.upload(free_v)); HIPCK(p, dbs.upload(blk_start)); HIPCK(p, dbsrc.upload(blk_src));
-            HIPCK(p, dbdiag.upload(blk_diag)); HIPCK(p, dbrow.upload(blk_row)); HIPCK(p, ddg.upload(dg_blk)); HIPCK(p, dmap.upload(blkmap));
+            HIPCK(p, dbdiag.upload(blk_diag)); HIPCK(p, dbrow.upload(blk_row)); HIPCK(p, ddg.upload(dg_blk));
+            if (!sparse) HIPCK(p, dmap.upload(blkmap));
             HIPCK(p, dErec.alloc((size_t)PGO_REC * std::max(ne, 1))); HIPCK(p, dHblk.alloc((size_t)36 * std::max(nblk, 1))); HIPCK(p, db.alloc(P));
-            HIPCK(p, sys.alloc(sysn, false)); HIPCK(p, Lfac.alloc(sysn)); HIPCK(p, xx.alloc(ld));
-            HIPCK(p, Linv.alloc((size_t)(Ppad / TILE) * TILE * TILE)); HIPCK(p, flags.alloc(Ppad / TILE)); HIPCK(p, LT32.alloc((size_t)Ppad * 64)); HIPCK(p, rd32.alloc(Ppad));
-            HIPCK(p, cflags.alloc((size_t)(Ppad / 32 + 2) * (Ppad / 32)));
-            if (Ppad / 32 <= NINV_MAX_T) HIPCK(p, Ninv.alloc((size_t)2 * Ppad * ld));
+            if (sparse) {
+                HIPCK(p, xx.alloc(P));
+                HIPCK(p, sp_m.upload(plan.f_m)); HIPCK(p, sp_np.upload(plan.f_np)); HIPCK(p, sp_row0.upload(plan.f_row0)); HIPCK(p, sp_rows.upload(plan.rows));
+                HIPCK(p, sp_umap.upload(plan.umap)); HIPCK(p, sp_chs.upload(plan.ch_start)); HIPCK(p, sp_ass.upload(plan.as_start)); HIPCK(p, sp_as.upload(plan.as));
+                HIPCK(p, sp_lv.upload(plan.lv)); HIPCK(p, sp_off.upload(plan.f_off)); HIPCK(p, sp_roff.upload(plan.f_roff));
+                if (plan.ch.empty()) plan.ch.assign(1, 0);
+                HIPCK(p, sp_ch.upload(plan.ch)); HIPCK(p, sp_F.alloc((size_t)plan.fsize, false)); HIPCK(p, sp_R.alloc((size_t)plan.rsize, false));
+            } else {
+                HIPCK(p, sys.alloc(sysn, false)); HIPCK(p, Lfac.alloc(sysn)); HIPCK(p, xx.alloc(ld));
+                HIPCK(p, Linv.alloc((size_t)(Ppad / TILE) * TILE * TILE)); HIPCK(p, flags.alloc(Ppad / TILE)); HIPCK(p, LT32.alloc((size_t)Ppad * 64)); HIPCK(p, rd32.alloc(Ppad));
+                HIPCK(p, cflags.alloc((size_t)(Ppad / 32 + 2) * (Ppad / 32)));
+                if (Ppad / 32 <= NINV_MAX_T) HIPCK(p, Ninv.alloc((size_t)2 * Ppad * ld));
+            }
         }
         HIPCK(p, plba_stream_wait(p, s));
     }
@@ -540,6 +570,18 @@ int plba_optimize_pose_graph(plba_problem* p, plba_pose_graph* g, int max_iters,
     d.X = dX.p; d.Xs = dXs.p; d.cnt = dcnt.p; d.free_v = dfree.p; d.ei = dei.p; d.ej = dej.p; d.Zi = dZi.p; d.info = dInfo.p;
     d.erec = dErec.p; d.echi = dEchi.p; d.blk_start = dbs.p; d.blk_src = dbsrc.p; d.blk_diag = dbdiag.p; d.blk_row = dbrow.p; d.dg_blk = ddg.p; d.blkmap = dmap.p;
     d.Hblk = dHblk.p; d.b = db.p; d.sys = sys.p; d.x = xx.p; d.ctl = dctl.p; d.mail = reinterpret_cast<PgoMail*>(p->d_mail); d.trace = dtrace.p;
+    PgoSparseDev sd; memset(&sd, 0, sizeof sd);
+    if (sparse && run) {
+        sd.f_m = sp_m.p; sd.f_np = sp_np.p; sd.f_row0 = sp_row0.p; sd.rows = sp_rows.p; sd.umap = sp_umap.p; sd.ch_start = sp_chs.p; sd.ch = sp_ch.p;
+        sd.as_start = sp_ass.p; sd.as = sp_as.p; sd.lv = sp_lv.p; sd.f_off = sp_off.p; sd.f_roff = sp_roff.p; sd.F = sp_F.p; sd.R = sp_R.p;
+        sd.Hblk = dHblk.p; sd.b = db.p; sd.x = xx.p; sd.c = &dctl.p->c; sd.done = &dctl.p->done;
+        size_t bytes = 0;
+        auto add = [&](const auto& a) { bytes += a.n * sizeof(*a.p); };
+        add(dX); add(dXs); add(dcnt); add(dZi); add(dInfo); add(dei); add(dej); add(dEchi); add(dctl); add(dtrace); add(dfree); add(dbs); add(dbsrc);
+        add(dbdiag); add(dbrow); add(ddg); add(dErec); add(dHblk); add(db); add(xx); add(sp_m); add(sp_np); add(sp_row0); add(sp_rows); add(sp_umap);
+        add(sp_chs); add(sp_ch); add(sp_ass); add(sp_as); add(sp_lv); add(sp_off); add(sp_roff); add(sp_F); add(sp_R);
+        p->pgo_sparse[6] = (double)bytes;
+    }
     DevBuf dd; memset(&dd, 0, sizeof dd);
     dd.P = P; dd.Ppad = Ppad; dd.ld = ld; dd.sys = sys.p; dd.Lfac = Lfac.p; dd.x = xx.p; dd.ctrl = &dctl.p->c; dd.Linv = Linv.p; dd.flow_flags = flags.p; dd.LTblk = LT32.p; dd.Linv32 = LT32.p; dd.rdblk = rd32.p;
     dd.fb = (p->opt.factor_block == 64) ? 64 : 32; dd.chol_flags = cflags.p; dd.flow = p->opt.factor_flow != 0; dd.wide = p->opt.wide_steps != 0 && !dd.flow;
@@ -559,9 +601,12 @@ int plba_optimize_pose_graph(plba_problem* p, plba_pose_graph* g, int max_iters,
             hipLaunchKernelGGL(k_pgo_edges<true>, eg, dim3(64), 0, s, d);
             hipLaunchKernelGGL(k_pgo_sum, bg, dim3(256), 0, s, d);
             hipLaunchKernelGGL(k_pgo_iter, dim3(1), dim3(256), 0, s, d);
-            hipLaunchKernelGGL(k_pgo_fill, fg, dim3(256), 0, s, d);
-            launch_cholesky(dd, p->opt.use_mfma != 0, step + 1, s);      // (not gated: after the run has ended it factors the identity, at most one step of it)
-            launch_trsv_back(dd, p->opt.use_mfma != 0, step + 1, s);
+            if (sparse) pgo_sparse_launch(sd, plan, s);
+            else {
+                hipLaunchKernelGGL(k_pgo_fill, fg, dim3(256), 0, s, d);
+                launch_cholesky(dd, p->opt.use_mfma != 0, step + 1, s);      // (not gated: after the run has ended it factors the identity, at most one step of it)
+                launch_trsv_back(dd, p->opt.use_mfma != 0, step + 1, s);
+            }
             hipLaunchKernelGGL(k_pgo_update, vg, dim3(64), 0, s, d);
             hipLaunchKernelGGL(k_pgo_edges<false>, eg, dim3(64), 0, s, d);
             hipLaunchKernelGGL(k_pgo_decide, dim3(1), dim3(256), 0, s, d, seq);

@@ -305,6 +305,7 @@ struct plba_problem {
     bool prior_changed = false;           // the prior changed but the window did not: the next prepare() rebuilds (plba_slide_window stays allowed)
     int pr_m = 0;                         // dropped dimension of the device-made prior (plba_get_prior)
     plba::MargPending* mp = nullptr;      // the marginalization that makes it, while it may still be in the stream (resolved by its first consumer)
+    double pgo_sparse[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // last plba_optimize_pose_graph (plba_debug_get "pgo_sparse", include/plba.h)
     long host_waits = 0;                  // times the library blocked the calling thread on the device (plba_debug_get "host_waits")
     plba::Robust rob;
     // shard
