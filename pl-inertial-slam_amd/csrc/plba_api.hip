@@ -1682,6 +1682,7 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
     //   8 <= T < 24  : the two-ended ("twin") form of the multi-launch factorisation (plba_dense.hip): same kernels, the two ends
     //                  of the band eliminated side by side in each launch
     p->band_ok = false; p->twin_ok = false;
+    for (double& v : p->plan_twin) v = 0.0;
     p->dd.band = 0; p->dd.twin_m0 = 0; p->dd.twin_fac = nullptr; p->dd.cs_order = nullptr; p->dd.perm = nullptr; p->dd.xmap = nullptr; p->dd.alt = nullptr; p->dd.alt2 = nullptr;
     p->dd.wtw = nullptr;
     if (p->chain_ok && p->lm_ok && p->world <= 1) {      // fused landmark path on one GPU: the chain Schur complement's W^T W tiles are formed in the gather launch
@@ -1689,6 +1690,7 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
         HIPCK(p, p->d_wtw.alloc((size_t)(T * (T + 1) / 2 + T) * 1024, false));
         p->dd.wtw = p->d_wtw.p;
     }
+    int plan_hbt = -1;      // (debug_get "solver_plan": the band as measured, -1 = not measured)
     if (p->chain_ok && p->opt.band_solve && !p->dv.flow && !p->dv.wide) {      // (sharded runs: the lists above hold the GLOBAL structure)
         const ChainView& cv = p->cv;
         const int T = cv.Pdpad / 32;
@@ -1892,12 +1894,19 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
                     p->dd.twin_m0 = m0; p->dd.twin_fac = p->d_twin_fac.p; p->dd.perm = p->d_twin_perm.p; p->dd.xmap = p->d_twin_xmap.p;
                     p->dd.alt = p->d_twin_alt.p; p->dd.alt2 = p->d_twin_alt.p + (size_t)(cv.Pdpad + TILE) * cv.Pdpad;
                     p->twin_ok = true;
+                    // the plan as chosen, for debug_get "solver_plan": first-stage chains in natural order, the separators between them
+                    std::vector<std::pair<int, int>> nat;
+                    for (const auto& ch : chains) if (ch.stage == 0) nat.push_back({ch.nat0, ch.len});
+                    p->plan_twin[0] = (double)nat.size(); p->plan_twin[1] = chains.size() > nat.size() ? 1.0 : 0.0;
+                    for (size_t q = 0; q + 1 < nat.size() && q < 3; ++q) p->plan_twin[2 + q] = (double)(nat[q + 1].first - nat[q].first - nat[q].second);
                 }
             }
+            plan_hbt = hbt;
         }
         if (ptime) fprintf(stderr, "[prepare] dense system: %d dims, %d tiles, band %d sub-diagonal tiles -> %s\n", cv.Pd, T, hbt, p->band_ok ? "banded twisted solve in LDS" : p->twin_ok ? "multi-chain multi-launch factorisation" : "dense path");
         if (ptime && p->twin_ok) fprintf(stderr, "[prepare] %d chains, %d + %d dependent launches\n", p->twinv.nchains, p->twinv.nlaunch, p->twinv.T - p->twinv.m0 - 1);
     }
+    p->plan_hbt = plan_hbt;
     HIPCK(p, darr_flush());
     // the structure is complete: remember it
     p->sc.dd = p->dd; p->sc.alist = d.alist; p->sc.nalist = d.nalist; p->sc.xlist = d.xlist; p->sc.nxlist = d.nxlist; p->sc.Ninv = d.Ninv; p->sc.Nwork = d.Nwork; p->sc.dbgbuf = d.dbgbuf;
@@ -3050,6 +3059,14 @@ int plba_debug_get(plba_problem* p, const char* what, double* out, size_t cap, s
     else if (w == "dense_dim") v = {(double)(p->chain_ok ? p->cv.Pd : p->P)};
     else if (w == "band") v = {(double)(p->band_ok ? 1 : 0)};
     else if (w == "twin") v = {(double)(p->twin_ok ? 1 : 0)};
+    else if (w == "solver_plan") {      // which form of the reduced-camera solve this window takes (tests/test_solver_accuracy.py):
+        // [0] form: 0 = the pose system itself (no chain elimination), 1 = compact system, one launch per tile, 2 = multi-chain, 3 = in-LDS band
+        // [1] 32-column tiles of the system factored  [2] explicit L^-T in use  [3] sub-diagonal tiles of the band (-1: not measured)
+        // [4] first-stage chains  [5] nested second stage  [6..8] separator widths in tiles  [9] nA  [10] nB (band sweeps)
+        const bool ninv = !p->band_ok && (p->chain_ok ? p->dd.Ninv : p->dv.Ninv) != nullptr;
+        v = {(double)(p->band_ok ? 3 : p->twin_ok ? 2 : p->chain_ok ? 1 : 0), (double)((p->chain_ok ? p->cv.Pdpad : p->Ppad) / 32), ninv ? 1.0 : 0.0, (double)p->plan_hbt,
+             p->plan_twin[0], p->plan_twin[1], p->plan_twin[2], p->plan_twin[3], p->plan_twin[4], (double)(p->band_ok ? p->bandv.nA : 0), (double)(p->band_ok ? p->bandv.nB : 0)};
+    }
     else if (w == "fact_launches_estimate") v = {(double)p->seg_launch_est};      // what the segment-length choice expected (twin_launch_estimate): fact_launches + 1 when the plan is built
     else if (w == "fact_launches") {      // dependent launches of one factorisation between the profile events 11 and 12 (bench.py's roofline)
         if (p->band_ok) v = {2.0};

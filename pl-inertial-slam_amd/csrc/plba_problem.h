@@ -371,6 +371,8 @@ struct plba_problem {
     bool band_ok = false;                       // the compact dense system is banded: twisted in-LDS solver (plba_band.hip)
     plba::BandView bandv{};
     plba::DArr<double> d_band_L, d_band_y, d_band_mid;
+    int plan_hbt = -1;                          // plba_debug_get "solver_plan": the measured band (sub-diagonal tiles), -1 = not measured;
+    double plan_twin[5] = {0, 0, 0, 0, 0};      // ... the multi-chain plan: first-stage chains, nested, up to three separator widths
     std::vector<int32_t> h_pidx, h_seg_col, h_alist;      // host copies of the chain maps / assembly list (band measurement)
     // fused landmark-major passes (options.lm_fused; plba_lm_dev.h)
     bool lm_ok = false;                         // this upload runs them (structure permitting: chain path, <= 16 observations per landmark — wide groups for 9 .. 16 —, none twice from one keyframe)

@@ -1,5 +1,5 @@
 """The 32 x 32 tile factorisation of the reduced-camera solve (csrc/plba_factor32_dev.h: two 16-column DPP sweeps of one wave, MFMA coupling
-blocks) on its own: tools/test_factor32.hip factors a graded SPD tile (entries over four decades) with it and with the look-ahead
+blocks) on its own: tools/test_factor32.hip factors graded SPD tiles (flat, entries over four and over fifteen decades; three seeds each) with it and with the look-ahead
 pipeline it replaced (csrc/plba_dense_dev.h, still used by the dataflow and 64-column forms) and prints the residuals of both.
 Replaces the diagonal-tile step of g2o's LinearSolverEigen."""
 import os
@@ -29,14 +29,31 @@ def test_tile_tool_builds():
     assert os.access(_build(), os.X_OK)
 
 
+ROW = re.compile(r"mode (\d) \((\w+)\): err ([\w ]+), solver_ok (\d), \|L L\^T - A\| \(scaled\) (\S+), \|Linv L - I\| (\S+), \|Linv - kept\| (\S+), upper part (\S+), cycles per tile (\d+)")
+GRADES = ["0", "0.0625", "0.25"]      # entry (i, j) carries 10^((i + j) * grade): flat, four decades (the matrix this test began with), fifteen
+SEEDS = ["7", "11", "13"]
+
+
 @pytest.mark.gpu
 def test_tile_factor_and_inverse():
-    out = subprocess.run([_build()], capture_output=True, text=True, timeout=120).stdout
-    rows = re.findall(r"mode (\d) \((\w+)\): err ([\w ]+), solver_ok (\d), \|L L\^T - A\| \(scaled\) (\S+), \|Linv L - I\| (\S+), \|Linv - kept\| (\S+), upper part (\S+), cycles per tile (\d+)", out)
-    assert len(rows) == 2, out
-    for mode, name, err, ok, e1, e2, e3, up, cyc in rows:
-        assert err == "no error" and ok == "1", (name, err, ok)
-        assert float(e1) < 1e-14 and float(e2) < 1e-13, (name, e1, e2)      # L L^T = A entrywise against sqrt(a_ii a_jj); L^-1 L = I
-        assert float(e3) == 0.0 and float(up) == 0.0, (name, e3, up)        # the copy kept in LDS is the published one; strictly lower triangular outputs
-    new, old = int(rows[1][8]), int(rows[0][8])
-    assert new < old, (new, old)      # the point of the exercise (10.7 k against 13.3 k cycles when written)
+    """Bounds: |L L^T - A| (scaled) < 1e-14 and |L^-1 L - I| < 1e-13 wherever the look-ahead pipeline — the second, independent implementation
+    printed beside the new one — meets them too; where it does not (steep grading: L^-1 L - I grows with the tile's condition number for
+    any fp64 inverse), 4 x the old pipeline's value for that matrix.  The table of both is in DESIGN.md section 5."""
+    exe = _build()
+    for grade in GRADES:
+        for seed in SEEDS:
+            out = subprocess.run([exe, grade, seed], capture_output=True, text=True, timeout=120).stdout
+            rows = ROW.findall(out)
+            assert len(rows) == 2, out
+            old_e1, old_e2 = float(rows[0][4]), float(rows[0][5])
+            print("grade %s seed %s: |L L^T - A| old %.2e new %.2e, |Linv L - I| old %.2e new %.2e, cycles old %s new %s" % (
+                grade, seed, old_e1, float(rows[1][4]), old_e2, float(rows[1][5]), rows[0][8], rows[1][8]))
+            b1 = 1e-14 if old_e1 < 1e-14 else 4 * old_e1
+            b2 = 1e-13 if old_e2 < 1e-13 else 4 * old_e2
+            for mode, name, err, ok, e1, e2, e3, up, cyc in rows:      # (the old pipeline meets 4 x its own value trivially)
+                assert err == "no error" and ok == "1", (grade, seed, name, err, ok)
+                assert float(e1) < b1 and float(e2) < b2, (grade, seed, name, e1, e2, b1, b2)      # L L^T = A entrywise against sqrt(a_ii a_jj); L^-1 L = I
+                assert float(e3) == 0.0 and float(up) == 0.0, (grade, seed, name, e3, up)            # the copy kept in LDS is the published one; strictly lower triangular outputs
+            if (grade, seed) == ("0.0625", "7"):
+                new, old = int(rows[1][8]), int(rows[0][8])
+                assert new < old, (new, old)      # the point of the exercise (10.7 k against 13.3 k cycles when written)

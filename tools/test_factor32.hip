@@ -1,4 +1,5 @@
 // standalone check + timing of factor32_dpp against lookahead_factor32 (run on the GPU box)
+// usage: test_factor32 [grading exponent, default 1/16: entry (i, j) carries 10^((i + j) * exponent)] [seed, default 7]
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -33,12 +34,14 @@ __global__ __launch_bounds__(256) void k_test(DevBuf d, const double* A, double*
     }
 }
 
-int main() {
+int main(int argc, char** argv) {
     const int n = 32;
+    const double grade = argc > 1 ? atof(argv[1]) : 1.0 / 16.0;
+    const unsigned seed = argc > 2 ? (unsigned)atoi(argv[2]) : 7u;
     std::vector<double> A(n * n), M(n * n);
-    srand(7);
+    srand(seed);
     for (auto& v : M) v = (rand() / (double)RAND_MAX - 0.5);
-    for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) { double s = 0; for (int k = 0; k < n; ++k) s += M[i * n + k] * M[j * n + k]; A[i * n + j] = s * std::pow(10.0, (i + j) / 16.0) + (i == j ? 3.0 * std::pow(10.0, i / 8.0) : 0.0); }
+    for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) { double s = 0; for (int k = 0; k < n; ++k) s += M[i * n + k] * M[j * n + k]; A[i * n + j] = s * std::pow(10.0, (i + j) * grade) + (i == j ? 3.0 * std::pow(10.0, 2.0 * i * grade) : 0.0); }
     double *dA, *dL, *dI, *dK; Ctrl* dc; unsigned long long* dcy;
     hipMalloc(&dA, 8192); hipMalloc(&dL, 8192); hipMalloc(&dI, 8192); hipMalloc(&dK, 8192); hipMalloc(&dc, sizeof(Ctrl)); hipMalloc(&dcy, 128);
     hipMemcpy(dA, A.data(), 8192, hipMemcpyHostToDevice);
