@@ -217,6 +217,7 @@ def preintegrate(omega, acc, dt):
     for s in range(S):
         w, a = omega[:, s], acc[:, s]
         dRk = exp_so3(w * dt)
+        dRk[np.linalg.norm(w * dt, axis=-1) < 1e-10] = I3      # Expmap, IMU/IMUPreintegrator.h:85-90: no rotation at all below 1e-10
         Jr = jr_so3(w * dt)
         Sa = hat(a)
         RS = dR @ Sa

@@ -76,6 +76,9 @@ def _check_preint(pkg, new_problem, tol):
     for m in range(g["meta"]["M"]):
         ref = np.array(g["cov_diag"][m])
         assert np.abs(np.diag(out[m, 60:141].reshape(9, 9)) - ref).max() <= tol * np.abs(ref).max()
+        for b in range(3):      # ... and the P, V, phi diagonals each on their own scale (phi's is 1e-4 of V's)
+            seg = slice(3 * b, 3 * b + 3)
+            assert np.abs(np.diag(out[m, 60:141].reshape(9, 9))[seg] - ref[seg]).max() <= tol * np.abs(ref[seg]).max(), (m, b)
     assert np.allclose(out[:, 141], g["dt"], rtol=0, atol=1e-15)
     assert np.abs(out).sum() == pytest.approx(g["checksum"], rel=tol)
 

@@ -129,6 +129,21 @@ void shim_gravity_oplus(const double* g3, const double* u2, double* out3) {
     VertexGravityW v; v.setEstimate(Vector3d(g3[0], g3[1], g3[2])); v.oplusImpl(u2);
     for (int i = 0; i < 3; ++i) out3[i] = v.estimate()[i];
 }
+// IMUPreintegrator::reset + update over a whole step list (w3 / a3 bias-corrected), through the class's own accessors
+void shim_preintegrate(int n, const double* w3, const double* a3, const double* dt, double* out142) {
+    IMUPreintegrator M;
+    M.reset();
+    for (int s = 0; s < n; ++s) M.update(Vector3d(w3[3 * s], w3[3 * s + 1], w3[3 * s + 2]), Vector3d(a3[3 * s], a3[3 * s + 1], a3[3 * s + 2]), dt[s]);
+    double* o = out142;
+    const Vector3d P = M.getDeltaP(), V = M.getDeltaV();
+    for (int i = 0; i < 3; ++i) *o++ = P[i];
+    for (int i = 0; i < 3; ++i) *o++ = V[i];
+    const Matrix3d blocks[6] = {M.getDeltaR(), M.getJPBiasg(), M.getJPBiasa(), M.getJVBiasg(), M.getJVBiasa(), M.getJRBiasg()};
+    for (const Matrix3d& B : blocks) for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) *o++ = B(i, j);
+    const Matrix9d C = M.getCovPVPhi();
+    for (int i = 0; i < 9; ++i) for (int j = 0; j < 9; ++j) *o++ = C(i, j);
+    *o = M.getDeltaTime();
+}
 void shim_navstate_edge(const double* gw, const double* navi, const double* navj, const double* pre142, int with_gw_vertex,
                         double* err15, double* Ji225, double* Jj225, double* Jg30) {
     VertexNavState vi, vj; vi.setEstimate(make_nav(navi)); vj.setEstimate(make_nav(navj));
