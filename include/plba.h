@@ -229,7 +229,11 @@ int plba_get_levels(plba_problem* p, plba_edge_kind kind, uint8_t* level);
  *     let plba_marginalize_to_prior have made it before the slide.
  * point_map[Np_before] / line_map[Nl_before] (optional) receive each old landmark's new index or -1.  The structure the next
  * plba_optimize builds — and therefore every result, bit for bit — is that of a fresh handle given the same window through
- * plba_set_* (tests/test_slide_window.py).  One GPU only (a sharded problem takes a fresh upload). */
+ * plba_set_* (tests/test_slide_window.py).  One GPU only (a sharded problem takes a fresh upload).
+ * A call that returns an error — a refused argument or a device error — leaves the resident window as it was: not edited, still
+ * resident, and a later valid slide goes through.
+ * The robust kernel switches (plba_set_robust) are NOT restored by a slide: after the previous call's gating the point / line
+ * kernels are off, so call plba_set_robust again for the new window, as a new graph has them again in the reference (:5937). */
 typedef struct {
     int n_drop;
     const uint8_t* drop_point;      /* [Np_before] 1 = leaves too; may be NULL */

@@ -212,6 +212,52 @@ class Lib:
         return o
 
 
+def make_slide(d):
+    """The plba_slide of include/plba.h for `d` as window.slide_delta() makes it; returns (struct, arrays its pointers refer to)."""
+    keep = []
+
+    def f64(a, shape=None):
+        if a is None:
+            return None
+        a = _f64(a, shape); keep.append(a); return _dp(a)
+
+    def i32(a):
+        if a is None:
+            return None
+        a = _i32(a); keep.append(a); return _ip(a)
+
+    def u8(a):
+        if a is None:
+            return None
+        a = _u8(a); keep.append(a); return _up(a)
+    s = Slide()
+    s.n_drop = int(d.get("n_drop", 0))
+    s.drop_point, s.drop_line = u8(d.get("drop_point")), u8(d.get("drop_line"))
+    s.drop_point_obs, s.drop_line_obs = u8(d.get("drop_point_obs")), u8(d.get("drop_line_obs"))
+    k = d.get("kf")
+    s.K_add = 0 if k is None else len(k["vid_pvr"])
+    if k is not None:
+        s.vid_pvr, s.vid_bias = i32(k["vid_pvr"]), i32(k.get("vid_bias"))
+        s.P3, s.V3, s.q_xyzw4 = f64(k["P"]), f64(k["V"]), f64(k["q"])
+        s.bg3, s.ba3, s.dbg3, s.dba3 = f64(k.get("bg")), f64(k.get("ba")), f64(k.get("dbg")), f64(k.get("dba"))
+    s.fixed_pvr, s.fixed_bias = u8(d.get("fixed_pvr")), u8(d.get("fixed_bias"))
+    im = d.get("imu")
+    s.M_add = 0 if im is None else len(im["kf_i"])
+    if im is not None:
+        s.imu_kf_i, s.imu_kf_j = i32(im["kf_i"]), i32(im["kf_j"])
+        s.preint142, s.info_pvr81, s.info_bias36 = f64(im["preint"], (-1, 142)), f64(im["info_pvr"], (-1, 81)), f64(im["info_bias"], (-1, 36))
+    pts, lns = d.get("points"), d.get("lines")
+    s.Np_add = 0 if pts is None else len(pts); s.xyz3 = f64(pts, (-1, 3)) if s.Np_add else None; s.point_fixed = u8(d.get("point_fixed"))
+    s.Nl_add = 0 if lns is None else len(lns); s.sPeP6 = f64(lns, (-1, 6)) if s.Nl_add else None; s.line_fixed = u8(d.get("line_fixed"))
+    s.Ep_add = len(d["po_pt"]) if d.get("po_pt") is not None else 0
+    if s.Ep_add:
+        s.po_pt, s.po_kf, s.uv2, s.po_inv_sigma2 = i32(d["po_pt"]), i32(d["po_kf"]), f64(d["po_uv"], (-1, 2)), f64(d.get("po_w"))
+    s.El_add = len(d["lo_ln"]) if d.get("lo_ln") is not None else 0
+    if s.El_add:
+        s.lo_ln, s.lo_kf, s.l3, s.lo_inv_sigma2 = i32(d["lo_ln"]), i32(d["lo_kf"]), f64(d["lo_l"], (-1, 3)), f64(d.get("lo_w"))
+    return s, keep
+
+
 class Problem:
     """One BA problem = one g2o::SparseOptimizer of the reference call site
     (src/mapHandler.cpp:5787-5797), behind the C ABI."""
@@ -563,47 +609,7 @@ class Problem:
     def slide_window(self, d):
         """plba_slide_window: `d` as window.slide_delta() makes it — n_drop, the appended keyframes / IMU edges / landmarks / observations,
         optional drop masks and the new window's fixed flags.  Returns (point_map, line_map): each old landmark's new index or -1."""
-        keep = []      # the arrays behind the struct's pointers stay alive until the call returns
-
-        def f64(a, shape=None):
-            if a is None:
-                return None
-            a = _f64(a, shape); keep.append(a); return _dp(a)
-
-        def i32(a):
-            if a is None:
-                return None
-            a = _i32(a); keep.append(a); return _ip(a)
-
-        def u8(a):
-            if a is None:
-                return None
-            a = _u8(a); keep.append(a); return _up(a)
-        s = Slide()
-        s.n_drop = int(d.get("n_drop", 0))
-        s.drop_point, s.drop_line = u8(d.get("drop_point")), u8(d.get("drop_line"))
-        s.drop_point_obs, s.drop_line_obs = u8(d.get("drop_point_obs")), u8(d.get("drop_line_obs"))
-        k = d.get("kf")
-        s.K_add = 0 if k is None else len(k["vid_pvr"])
-        if k is not None:
-            s.vid_pvr, s.vid_bias = i32(k["vid_pvr"]), i32(k.get("vid_bias"))
-            s.P3, s.V3, s.q_xyzw4 = f64(k["P"]), f64(k["V"]), f64(k["q"])
-            s.bg3, s.ba3, s.dbg3, s.dba3 = f64(k.get("bg")), f64(k.get("ba")), f64(k.get("dbg")), f64(k.get("dba"))
-        s.fixed_pvr, s.fixed_bias = u8(d.get("fixed_pvr")), u8(d.get("fixed_bias"))
-        im = d.get("imu")
-        s.M_add = 0 if im is None else len(im["kf_i"])
-        if im is not None:
-            s.imu_kf_i, s.imu_kf_j = i32(im["kf_i"]), i32(im["kf_j"])
-            s.preint142, s.info_pvr81, s.info_bias36 = f64(im["preint"], (-1, 142)), f64(im["info_pvr"], (-1, 81)), f64(im["info_bias"], (-1, 36))
-        pts, lns = d.get("points"), d.get("lines")
-        s.Np_add = 0 if pts is None else len(pts); s.xyz3 = f64(pts, (-1, 3)) if s.Np_add else None; s.point_fixed = u8(d.get("point_fixed"))
-        s.Nl_add = 0 if lns is None else len(lns); s.sPeP6 = f64(lns, (-1, 6)) if s.Nl_add else None; s.line_fixed = u8(d.get("line_fixed"))
-        s.Ep_add = len(d["po_pt"]) if d.get("po_pt") is not None else 0
-        if s.Ep_add:
-            s.po_pt, s.po_kf, s.uv2, s.po_inv_sigma2 = i32(d["po_pt"]), i32(d["po_kf"]), f64(d["po_uv"], (-1, 2)), f64(d.get("po_w"))
-        s.El_add = len(d["lo_ln"]) if d.get("lo_ln") is not None else 0
-        if s.El_add:
-            s.lo_ln, s.lo_kf, s.l3, s.lo_inv_sigma2 = i32(d["lo_ln"]), i32(d["lo_kf"]), f64(d["lo_l"], (-1, 3)), f64(d.get("lo_w"))
+        s, keep = make_slide(d)      # (`keep`: the arrays behind the struct's pointers stay alive until the call returns)
         pm = np.zeros(max(self.dims.get("Np", 0), 1), np.int32); lm = np.zeros(max(self.dims.get("Nl", 0), 1), np.int32)
         self.call("slide_window", C.byref(s), _ip(pm), _ip(lm))
         pm, lm = pm[:self.dims.get("Np", 0)], lm[:self.dims.get("Nl", 0)]

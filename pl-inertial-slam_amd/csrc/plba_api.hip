@@ -49,19 +49,14 @@ static void reset_for_reuse(plba_problem* p, const plba_options* opt) {
     p->ev_sample = false; p->trial_counter = 0; p->spec_lin = false; p->lin_in_span = false; p->prof_lin_launches = 0;
     p->marg_dbg.clear(); for (double& v : p->marg_path) v = 0.0;
     p->spec_hll = false;
-    p->have_cam = false; p->gw[0] = p->gw[1] = p->gw[2] = 0.0;
-    p->K = p->Np = p->Nl = p->Ep = p->El = p->M = 0;
-    p->vid_pvr.clear(); p->vid_bias.clear(); p->kf0.clear(); p->fix_pvr.clear(); p->fix_bias.clear(); p->lm0.clear(); p->lm_fixed.clear();
-    p->pts.clear(); p->lns.clear(); p->pt_fixed.clear(); p->ln_fixed.clear();
-    p->po_pt.clear(); p->po_kf.clear(); p->lo_ln.clear(); p->lo_kf.clear(); p->po_uv.clear(); p->po_w.clear(); p->lo_l.clear(); p->lo_w.clear();
-    p->level.clear(); p->imu_i.clear(); p->imu_j.clear(); p->imu_pre.clear(); p->imu_ipvr.clear(); p->imu_ibias.clear();
+    p->win.clear(); p->win_next.clear(); p->lm0.clear(); p->lm_fixed.clear();
     p->pr_n = p->pr_nv = 0; p->pr_vid.clear(); p->pr_size.clear(); p->pr_idx.clear(); p->pr_x0.clear(); p->pr_J0.clear(); p->pr_r0.clear();
     p->prior_dev = false; p->prior_changed = false; p->pr_m = 0; p->host_waits = 0;
     for (double& v : p->pgo_sparse) v = 0.0;
     memset(&p->rob, 0, sizeof p->rob);
     p->rank = 0; p->world = 1; p->xfn = nullptr; p->xuser = nullptr;
     p->dirty = true; p->P = p->Ppad = p->ld = p->L = p->E = 0; p->cur = 0;
-    p->carry_pts = p->carry_lns = p->carry_kf = p->carry_po = p->carry_lo = p->carry_obs_pending = false;
+    p->carry_obs_pending = false;
     p->ob_pos.clear(); p->flow_epoch = 0;
     p->lm_ok = false; p->lm_grouped = false; ++p->state_epoch; p->res_lm_epoch = 0; p->res_lm.clear(); p->lm_hist.clear();
     p->lm_chi_dirty = false; p->back_epoch = 0; p->lm_disable = false; p->lm_spec = false; p->assembled = false;
@@ -84,11 +79,6 @@ static void reset_for_reuse(plba_problem* p, const plba_options* opt) {
 
 static const int TRACE_CAP = 4096;
 static const int SCHUR_CHUNK = 256;   // entries of a keyframe pair per k_schur_pairs workgroup (512: no faster)
-
-static bool all_finite(const double* a, size_t n) {
-    for (size_t i = 0; i < n; ++i) if (!std::isfinite(a[i])) return false;
-    return true;
-}
 
 extern "C" {
 
@@ -219,14 +209,14 @@ int plba_set_stream(plba_problem* p, void* s) {
 
 int plba_set_camera(plba_problem* p, double fx, double fy, double cx, double cy, const double* Rbc, const double* Pbc) {
     if (!p || !Rbc || !Pbc) return PLBA_ERR_INVALID;
-    p->fx = fx; p->fy = fy; p->cx = cx; p->cy = cy;
-    memcpy(p->Rbc, Rbc, 72); memcpy(p->Pbc, Pbc, 24);
-    p->have_cam = true; p->dirty = true;
+    p->win.fx = fx; p->win.fy = fy; p->win.cx = cx; p->win.cy = cy;
+    memcpy(p->win.Rbc, Rbc, 72); memcpy(p->win.Pbc, Pbc, 24);
+    p->win.have_cam = true; p->dirty = true;
     return PLBA_OK;
 }
 int plba_set_gravity(plba_problem* p, const double* gw) {
     if (!p || !gw) return PLBA_ERR_INVALID;
-    memcpy(p->gw, gw, 24);
+    memcpy(p->win.gw, gw, 24);
     p->dirty = true;
     return PLBA_OK;
 }
@@ -236,21 +226,21 @@ int plba_set_keyframes(plba_problem* p, int K, const int32_t* vid_pvr, const int
     if (!p || K <= 0 || !vid_pvr || !P3 || !V3 || !q4) return PLBA_ERR_INVALID;
     for (int k = 1; k < K; ++k) if (vid_pvr[k] <= vid_pvr[k - 1]) FAIL(p, PLBA_ERR_INVALID, "keyframe vertex ids must be ascending");
     if (!all_finite(P3, 3 * (size_t)K) || !all_finite(V3, 3 * (size_t)K) || !all_finite(q4, 4 * (size_t)K)) FAIL(p, PLBA_ERR_NUMERIC, "non-finite keyframe state");
-    p->K = K; p->carry_kf = false;
-    p->vid_pvr.assign(vid_pvr, vid_pvr + K);
-    p->vid_bias.assign(K, -1);
-    p->kf0.assign((size_t)K * KF_STRIDE, 0.0);
-    p->fix_pvr.assign(K, 0); p->fix_bias.assign(K, 0);
+    p->win.K = K; p->win.carry_kf = false;
+    p->win.vid_pvr.assign(vid_pvr, vid_pvr + K);
+    p->win.vid_bias.assign(K, -1);
+    p->win.kf0.assign((size_t)K * KF_STRIDE, 0.0);
+    p->win.fix_pvr.assign(K, 0); p->win.fix_bias.assign(K, 0);
     for (int k = 0; k < K; ++k) {
-        double* s = &p->kf0[(size_t)k * KF_STRIDE];
-        if (vid_bias) p->vid_bias[k] = vid_bias[k];
+        double* s = &p->win.kf0[(size_t)k * KF_STRIDE];
+        if (vid_bias) p->win.vid_bias[k] = vid_bias[k];
         memcpy(s, P3 + 3 * k, 24); memcpy(s + 3, V3 + 3 * k, 24); memcpy(s + 6, q4 + 4 * k, 32);
         if (bg3) memcpy(s + 10, bg3 + 3 * k, 24);
         if (ba3) memcpy(s + 13, ba3 + 3 * k, 24);
         if (dbg3) memcpy(s + 16, dbg3 + 3 * k, 24);
         if (dba3) memcpy(s + 19, dba3 + 3 * k, 24);
-        if (fixed_pvr) p->fix_pvr[k] = fixed_pvr[k];
-        if (fixed_bias) p->fix_bias[k] = fixed_bias[k];
+        if (fixed_pvr) p->win.fix_pvr[k] = fixed_pvr[k];
+        if (fixed_bias) p->win.fix_bias[k] = fixed_bias[k];
     }
     p->dirty = true;
     return PLBA_OK;
@@ -258,29 +248,29 @@ int plba_set_keyframes(plba_problem* p, int K, const int32_t* vid_pvr, const int
 int plba_set_points(plba_problem* p, int Np, const double* xyz, const uint8_t* fixed) {
     if (!p || Np < 0 || (Np && !xyz)) return PLBA_ERR_INVALID;
     if (!all_finite(xyz, 3 * (size_t)Np)) FAIL(p, PLBA_ERR_NUMERIC, "non-finite point");
-    p->Np = Np;
-    p->pts.assign(xyz, xyz + 3 * (size_t)Np);
-    p->carry_pts = false;
-    p->pt_fixed.assign(Np, 0);
-    if (fixed) p->pt_fixed.assign(fixed, fixed + Np);
+    p->win.Np = Np;
+    p->win.pts.assign(xyz, xyz + 3 * (size_t)Np);
+    p->win.carry_pts = false;
+    p->win.pt_fixed.assign(Np, 0);
+    if (fixed) p->win.pt_fixed.assign(fixed, fixed + Np);
     p->dirty = true;
     return PLBA_OK;
 }
 int plba_set_lines(plba_problem* p, int Nl, const double* l, const uint8_t* fixed) {
     if (!p || Nl < 0 || (Nl && !l)) return PLBA_ERR_INVALID;
     if (!all_finite(l, 6 * (size_t)Nl)) FAIL(p, PLBA_ERR_NUMERIC, "non-finite line");
-    p->Nl = Nl;
-    p->lns.assign(l, l + 6 * (size_t)Nl);
-    p->carry_lns = false;
-    p->ln_fixed.assign(Nl, 0);
-    if (fixed) p->ln_fixed.assign(fixed, fixed + Nl);
+    p->win.Nl = Nl;
+    p->win.lns.assign(l, l + 6 * (size_t)Nl);
+    p->win.carry_lns = false;
+    p->win.ln_fixed.assign(Nl, 0);
+    if (fixed) p->win.ln_fixed.assign(fixed, fixed + Nl);
     p->dirty = true;
     return PLBA_OK;
 }
 static int check_obs(plba_problem* p, int E, const int32_t* lm, const int32_t* kf, int Nlm) {
     for (int e = 0; e < E; ++e) {
         if (lm[e] < 0 || lm[e] >= Nlm) FAIL(p, PLBA_ERR_INVALID, "observation %d: landmark index out of range", e);
-        if (kf[e] < 0 || kf[e] >= p->K) FAIL(p, PLBA_ERR_INVALID, "observation %d: keyframe index out of range", e);
+        if (kf[e] < 0 || kf[e] >= p->win.K) FAIL(p, PLBA_ERR_INVALID, "observation %d: keyframe index out of range", e);
         if (e && lm[e] < lm[e - 1]) FAIL(p, PLBA_ERR_INVALID, "observations must be landmark-major (sorted by landmark)");
     }
     for (int e = 0; e < E; ++e)
@@ -290,70 +280,73 @@ static int check_obs(plba_problem* p, int E, const int32_t* lm, const int32_t* k
 }
 int plba_set_point_obs(plba_problem* p, int Ep, const int32_t* pt, const int32_t* kf, const double* uv, const double* w) {
     if (!p || Ep < 0 || (Ep && (!pt || !kf || !uv))) return PLBA_ERR_INVALID;
-    if (!p->K) FAIL(p, PLBA_ERR_STATE, "set_keyframes first");
-    int rc = check_obs(p, Ep, pt, kf, p->Np);
+    if (!p->win.K) FAIL(p, PLBA_ERR_STATE, "set_keyframes first");
+    int rc = check_obs(p, Ep, pt, kf, p->win.Np);
     if (rc) return rc;
     if (!all_finite(uv, 2 * (size_t)Ep)) FAIL(p, PLBA_ERR_NUMERIC, "non-finite observation");
-    p->Ep = Ep;
-    p->po_pt.assign(pt, pt + Ep); p->po_kf.assign(kf, kf + Ep);
-    p->po_uv.assign(uv, uv + 2 * (size_t)Ep);
-    p->po_w.assign(Ep, 1.0);
-    if (w) for (int e = 0; e < Ep; ++e) p->po_w[e] = (double)(float)w[e];   // const float& invSigma2 (mapHandler.cpp:5340)
-    p->carry_po = false;
-    p->level.assign((size_t)p->Ep + p->El, 0);      // new edges are level 0 (g2o); a re-used handle does not inherit the previous window's
+    p->win.Ep = Ep;
+    p->win.po_pt.assign(pt, pt + Ep); p->win.po_kf.assign(kf, kf + Ep);
+    p->win.po_uv.assign(uv, uv + 2 * (size_t)Ep);
+    p->win.po_w.assign(Ep, 1.0);
+    if (w) for (int e = 0; e < Ep; ++e) p->win.po_w[e] = (double)(float)w[e];   // const float& invSigma2 (mapHandler.cpp:5340)
+    p->win.carry_po = false;
+    p->win.level.assign((size_t)p->win.Ep + p->win.El, 0);      // new edges are level 0 (g2o); a re-used handle does not inherit the previous window's
     p->dirty = true;
     return PLBA_OK;
 }
 int plba_set_line_obs(plba_problem* p, int El, const int32_t* ln, const int32_t* kf, const double* l3, const double* w) {
     if (!p || El < 0 || (El && (!ln || !kf || !l3))) return PLBA_ERR_INVALID;
-    if (!p->K) FAIL(p, PLBA_ERR_STATE, "set_keyframes first");
-    int rc = check_obs(p, El, ln, kf, p->Nl);
+    if (!p->win.K) FAIL(p, PLBA_ERR_STATE, "set_keyframes first");
+    int rc = check_obs(p, El, ln, kf, p->win.Nl);
     if (rc) return rc;
     if (!all_finite(l3, 3 * (size_t)El)) FAIL(p, PLBA_ERR_NUMERIC, "non-finite observation");
-    p->El = El;
-    p->lo_ln.assign(ln, ln + El); p->lo_kf.assign(kf, kf + El);
-    p->lo_l.assign(l3, l3 + 3 * (size_t)El);
-    p->lo_w.assign(El, 1.0);
-    if (w) for (int e = 0; e < El; ++e) p->lo_w[e] = (double)(float)w[e];
-    p->carry_lo = false;
+    p->win.El = El;
+    p->win.lo_ln.assign(ln, ln + El); p->win.lo_kf.assign(kf, kf + El);
+    p->win.lo_l.assign(l3, l3 + 3 * (size_t)El);
+    p->win.lo_w.assign(El, 1.0);
+    if (w) for (int e = 0; e < El; ++e) p->win.lo_w[e] = (double)(float)w[e];
+    p->win.carry_lo = false;
     // the new line edges are level 0; the POINT edges' levels stay (set_point_obs -> set_levels(POINT) -> set_line_obs used
     // to drop them).  plba_set_point_obs still resets both ranges: Ep moves the line range's offset.
-    p->level.resize((size_t)p->Ep + p->El);
-    std::fill(p->level.begin() + std::min((size_t)p->Ep, p->level.size()), p->level.end(), (uint8_t)0);
+    p->win.level.resize((size_t)p->win.Ep + p->win.El);
+    std::fill(p->win.level.begin() + std::min((size_t)p->win.Ep, p->win.level.size()), p->win.level.end(), (uint8_t)0);
     p->dirty = true;
     return PLBA_OK;
 }
 int plba_set_imu_edges(plba_problem* p, int M, const int32_t* ki, const int32_t* kj, const double* pre, const double* ipvr, const double* ibias) {
     if (!p || M < 0 || (M && (!ki || !kj || !pre || !ipvr || !ibias))) return PLBA_ERR_INVALID;
     for (int m = 0; m < M; ++m) {
-        if (ki[m] < 0 || ki[m] >= p->K || kj[m] < 0 || kj[m] >= p->K) FAIL(p, PLBA_ERR_INVALID, "imu edge %d: keyframe index", m);
-        if (p->vid_bias[ki[m]] < 0 || p->vid_bias[kj[m]] < 0) FAIL(p, PLBA_ERR_INVALID, "imu edge %d: keyframe without bias vertex", m);
+        if (ki[m] < 0 || ki[m] >= p->win.K || kj[m] < 0 || kj[m] >= p->win.K) FAIL(p, PLBA_ERR_INVALID, "imu edge %d: keyframe index", m);
+        if (p->win.vid_bias[ki[m]] < 0 || p->win.vid_bias[kj[m]] < 0) FAIL(p, PLBA_ERR_INVALID, "imu edge %d: keyframe without bias vertex", m);
     }
     if (!all_finite(pre, 142 * (size_t)M) || !all_finite(ipvr, 81 * (size_t)M)) FAIL(p, PLBA_ERR_NUMERIC, "non-finite IMU edge");
-    p->M = M;
-    p->imu_i.assign(ki, ki + M); p->imu_j.assign(kj, kj + M);
-    p->imu_pre.assign(pre, pre + 142 * (size_t)M);
-    p->imu_ipvr.assign(ipvr, ipvr + 81 * (size_t)M);
-    p->imu_ibias.assign(ibias, ibias + 36 * (size_t)M);
+    p->win.M = M;
+    p->win.imu_i.assign(ki, ki + M); p->win.imu_j.assign(kj, kj + M);
+    p->win.imu_pre.assign(pre, pre + 142 * (size_t)M);
+    p->win.imu_ipvr.assign(ipvr, ipvr + 81 * (size_t)M);
+    p->win.imu_ibias.assign(ibias, ibias + 36 * (size_t)M);
     p->dirty = true;
     return PLBA_OK;
 }
 int plba_set_prior(plba_problem* p, int n, int nv, const int32_t* vid, const int32_t* size, const int32_t* idx, const double* x0,
                    const double* J0, const double* r0) {
     if (!p) return PLBA_ERR_INVALID;
+    // validate, then touch: a refused call leaves the prior — host-made, device-made or still pending — exactly as it was
+    int tot = 0, nx = 0;
+    if (nv != 0) {
+        if (n <= 0 || nv < 0 || !vid || !size || !idx || !x0 || !J0 || !r0) return PLBA_ERR_INVALID;
+        for (int i = 0; i < nv; ++i) {
+            if (size[i] != 9 && size[i] != 6) FAIL(p, PLBA_ERR_INVALID, "Undefined size of marginalization vertex: %d", size[i]);
+            if (idx[i] < 0 || idx[i] + size[i] > n) FAIL(p, PLBA_ERR_INVALID, "prior vertex %d: idx out of range", i);
+            nx += size[i] == 9 ? 10 : 6;
+            tot += size[i];
+        }
+        if (tot != n) FAIL(p, PLBA_ERR_INVALID, "prior: sum of kept sizes %d != n %d", tot, n);
+    }
     marg_discard(p);      // a pending plba_marginalize_to_prior: waited for, its result dropped
     p->dirty = true;
     p->prior_dev = false; p->prior_changed = false; p->pr_m = 0;
     if (nv == 0) { p->pr_n = 0; p->pr_nv = 0; return PLBA_OK; }
-    if (n <= 0 || nv < 0 || !vid || !size || !idx || !x0 || !J0 || !r0) return PLBA_ERR_INVALID;
-    int tot = 0, nx = 0;
-    for (int i = 0; i < nv; ++i) {
-        if (size[i] != 9 && size[i] != 6) FAIL(p, PLBA_ERR_INVALID, "Undefined size of marginalization vertex: %d", size[i]);
-        if (idx[i] < 0 || idx[i] + size[i] > n) FAIL(p, PLBA_ERR_INVALID, "prior vertex %d: idx out of range", i);
-        nx += size[i] == 9 ? 10 : 6;
-        tot += size[i];
-    }
-    if (tot != n) FAIL(p, PLBA_ERR_INVALID, "prior: sum of kept sizes %d != n %d", tot, n);
     p->pr_n = n; p->pr_nv = nv;
     p->pr_vid.assign(vid, vid + nv); p->pr_size.assign(size, size + nv); p->pr_idx.assign(idx, idx + nv);
     p->pr_x0.assign(x0, x0 + nx);
@@ -522,7 +515,7 @@ private:
 // index), so that a group streams its inputs.  Per group and window-slot pair (p <= q) some landmark couples, one contribution to
 // the pose-pair block (kf[p], kf[q]); the gather lists hold them block by block in ascending group order (a fixed summation order).
 static bool lm_structure_fits(const plba_problem* p, const std::vector<int32_t>& lm_start) {
-    if (p->K >= 65536) return false;
+    if (p->win.K >= 65536) return false;
     for (int s = 0; s < p->L; ++s) if (lm_start[s + 1] - lm_start[s] > LMF_W2) return false;
     return true;      // (two observations of a landmark in one keyframe are refused at upload; build_lm_groups still checks and returns false)
 }
@@ -538,7 +531,7 @@ static void lm_fill_groups(const plba_problem* p, const std::vector<int32_t>& lm
     const uint8_t* const fixed = p->lm_fixed.data();
     int32_t* const o_slot = H.p_lm_slot; int32_t* const o_ob0 = H.p_lm_ob0; int32_t* const o_orig = H.p_ob_orig; uint8_t* const o_fixed = H.p_lm_fixed; uint8_t* const o_ws8 = H.p_lm_ws8;
     const int wmax = H.wmax;
-    const bool use_lut = p->K <= 256;
+    const bool use_lut = p->win.K <= 256;
     uint8_t lut[256];
     int bad = 0;
     for (int gi = H.gcut[t]; gi < H.gcut[t + 1]; ++gi) {
@@ -571,7 +564,7 @@ static bool lm_groups_finish(LmHost& H) {      // false: a keyframe observes a l
     return true;
 }
 static void build_lm_groups(const plba_problem* p, const std::vector<int32_t>& lm_start, const std::vector<int32_t>& ob_kf, LmHost& H) {
-    const int K = p->K, Np = p->Np, Nl = p->Nl, Ep = p->Ep, L = Np + Nl, E = (int)ob_kf.size();
+    const int K = p->win.K, Np = p->win.Np, Nl = p->win.Nl, Ep = p->win.Ep, L = Np + Nl, E = (int)ob_kf.size();
     H.cov.assign((size_t)K * K, 0);
     const bool gt = (p->opt.diag & PLBA_DIAG_TIMING) != 0;
     auto g0 = std::chrono::steady_clock::now();
@@ -593,7 +586,7 @@ static void build_lm_groups(const plba_problem* p, const std::vector<int32_t>& l
         if (!cus) { int dev = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256; }
         const int slots = 2 * cus;
         const long wg_steps = (Np - nwide_pt + 31) / 32 + (Nl - nwide_ln + 15) / 16 + (nwide_pt + 15) / 16 + (nwide_ln + 7) / 8;
-        const long cap1 = std::max<long>(32, (long)(1.12 * cus) - (p->M + 1) - (p->M / 4 + 1));      // one group per CU, with room for the IMU edge blocks and the chain segments
+        const long cap1 = std::max<long>(32, (long)(1.12 * cus) - (p->win.M + 1) - (p->win.M / 4 + 1));      // one group per CU, with room for the IMU edge blocks and the chain segments
         steps = (int)std::max<long>(1, (wg_steps + cap1 - 1) / cap1);
         if (steps > 16) {
             for (int R = 1; R <= 64; ++R) {
@@ -857,8 +850,9 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
     if (reads_prior && p->prior_changed) p->dirty = true;
     if (!p->dirty) return PLBA_OK;
     if (p->mp) { if (int rc = marg_resolve(p)) return rc; }      // the prior this window reads (plba_marginalize_to_prior)
-    if (!p->have_cam || !p->K) FAIL(p, PLBA_ERR_STATE, "camera and keyframes must be set before optimize");
-    if ((int)p->po_pt.size() != p->Ep) p->Ep = 0;
+    const Window& w = p->win;      // read-only here, but for the two repairs of a half-set window: Ep below, the levels' size further down
+    if (!w.have_cam || !w.K) FAIL(p, PLBA_ERR_STATE, "camera and keyframes must be set before optimize");
+    if ((int)w.po_pt.size() != w.Ep) p->win.Ep = 0;
     HIPCK(p, hipSetDevice(p->device));
     DArrStreamScope zero_fill_on(p->stream, p->have_ctx ? p->ctx.stage : nullptr);      // fresh buffers are cleared, and uploads queued, on the stream their kernels run on
     // the small ones among them in two blocks, one memset and one copy per flush (plba_problem.h, DevBatch)
@@ -875,7 +869,7 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
         b.u = b.uh ? p->d_batch_u.p : nullptr; b.ucap = DevBatch::UCAP; b.uused = b.udone = 0; b.n_batched = 0;
     }
     DevBatchScope batch_small(&p->batch);
-    const int K = p->K, Np = p->Np, Nl = p->Nl, Ep = p->Ep, El = p->El, M = p->M;
+    const int K = w.K, Np = w.Np, Nl = w.Nl, Ep = w.Ep, El = w.El, M = w.M;
     const int L = Np + Nl, E = Ep + El;
     p->L = L; p->E = E;
     // the observation arrays may refer to landmarks uploaded later/earlier: re-check ranges
@@ -885,11 +879,11 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
     // would leave the others blocked in the vote below.  The verdict is carried into that all-reduce and every rank fails together.
     bool local_invalid = false;
     auto invalid = [&](const char* fmt, int a, int b, int c, int d2, int e2) { if (!local_invalid) snprintf(p->err, sizeof p->err, fmt, a, b, c, d2, e2); local_invalid = true; };
-    for (int e = 0; e < Ep && !local_invalid; ++e) if (p->po_pt[e] >= Np || p->po_kf[e] >= K) invalid("point observation %d refers to point %d of %d / keyframe %d of %d", e, p->po_pt[e], Np, p->po_kf[e], K);
-    for (int e = 0; e < El && !local_invalid; ++e) if (p->lo_ln[e] >= Nl || p->lo_kf[e] >= K) invalid("line observation %d refers to line %d of %d / keyframe %d of %d", e, p->lo_ln[e], Nl, p->lo_kf[e], K);
+    for (int e = 0; e < Ep && !local_invalid; ++e) if (w.po_pt[e] >= Np || w.po_kf[e] >= K) invalid("point observation %d refers to point %d of %d / keyframe %d of %d", e, w.po_pt[e], Np, w.po_kf[e], K);
+    for (int e = 0; e < El && !local_invalid; ++e) if (w.lo_ln[e] >= Nl || w.lo_kf[e] >= K) invalid("line observation %d refers to line %d of %d / keyframe %d of %d", e, w.lo_ln[e], Nl, w.lo_kf[e], K);
     for (int m = 0; m < M && !local_invalid; ++m)
-        if (p->imu_i[m] >= K || p->imu_j[m] >= K || p->vid_bias[p->imu_i[m]] < 0 || p->vid_bias[p->imu_j[m]] < 0)
-            invalid("imu edge %d joins keyframes %d and %d of %d (edges of a previous window? set them again, or clear them with M = %d)", m, p->imu_i[m], p->imu_j[m], K, 0);
+        if (w.imu_i[m] >= K || w.imu_j[m] >= K || w.vid_bias[w.imu_i[m]] < 0 || w.vid_bias[w.imu_j[m]] < 0)
+            invalid("imu edge %d joins keyframes %d and %d of %d (edges of a previous window? set them again, or clear them with M = %d)", m, w.imu_i[m], w.imu_j[m], K, 0);
     if (local_invalid && p->world <= 1) return PLBA_ERR_INVALID;
     if (local_invalid) {      // take part in the window's vote (the first collective of every rank's prepare()) and return with the others
         std::vector<double> vote = {0.0, 1.0, 1.0};
@@ -899,7 +893,7 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
         HIPCK(p, plba_stream_wait(p, p->stream));
         return PLBA_ERR_INVALID;      // (p->err holds this rank's finding)
     }
-    if ((int)p->level.size() != E) p->level.assign(E, 0);
+    if ((int)w.level.size() != E) p->win.level.assign(E, 0);
     const bool ptime = (p->opt.diag & PLBA_DIAG_TIMING) != 0;
     auto pt0 = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) { if (!ptime) return; auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[prepare] %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - pt0).count()); pt0 = t; };
@@ -907,9 +901,9 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
     p->off_pvr.assign(K, -1); p->off_bias.assign(K, -1);
     int off = 0;
     for (int k = 0; k < K; ++k) {
-        const bool pv = !p->fix_pvr[k];
-        const bool bv = p->vid_bias[k] >= 0 && !p->fix_bias[k];
-        if (pv && bv && p->vid_bias[k] < p->vid_pvr[k]) { p->off_bias[k] = off; off += 6; p->off_pvr[k] = off; off += 9; }
+        const bool pv = !w.fix_pvr[k];
+        const bool bv = w.vid_bias[k] >= 0 && !w.fix_bias[k];
+        if (pv && bv && w.vid_bias[k] < w.vid_pvr[k]) { p->off_bias[k] = off; off += 6; p->off_pvr[k] = off; off += 9; }
         else {
             if (pv) { p->off_pvr[k] = off; off += 9; }
             if (bv) { p->off_bias[k] = off; off += 6; }
@@ -926,14 +920,14 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
     std::vector<int32_t> ob_kf(E), ob_slot(E), lm_start(L + 1, 0);
     std::vector<double> ob_w(E);
     // (a slid window's measurements and weights are on the device already: plba_slide_window)
-    const bool carry_obs = (p->carry_po || Ep == 0) && (p->carry_lo || El == 0) && (p->carry_po || p->carry_lo);
-    if ((p->carry_po || p->carry_lo) && !carry_obs) FAIL(p, PLBA_ERR_STATE, "after plba_slide_window set BOTH observation arrays again (plba_set_point_obs and plba_set_line_obs) or neither: the kept measurements live on the device");
+    const bool carry_obs = (w.carry_po || Ep == 0) && (w.carry_lo || El == 0) && (w.carry_po || w.carry_lo);
+    if ((w.carry_po || w.carry_lo) && !carry_obs) FAIL(p, PLBA_ERR_STATE, "after plba_slide_window set BOTH observation arrays again (plba_set_point_obs and plba_set_line_obs) or neither: the kept measurements live on the device");
     {
         int32_t* okf = ob_kf.data(); int32_t* osl = ob_slot.data(); int32_t* ls = lm_start.data(); double* ow = ob_w.data();
-        const int32_t* ppt = p->po_pt.data(); const int32_t* pkf = p->po_kf.data(); const int32_t* lln = p->lo_ln.data(); const int32_t* lkf = p->lo_kf.data();
+        const int32_t* ppt = w.po_pt.data(); const int32_t* pkf = w.po_kf.data(); const int32_t* lln = w.lo_ln.data(); const int32_t* lkf = w.lo_kf.data();
         for (int e = 0; e < Ep; ++e) { okf[e] = pkf[e]; osl[e] = ppt[e]; ls[ppt[e] + 1]++; }
         for (int e = 0; e < El; ++e) { okf[Ep + e] = lkf[e]; osl[Ep + e] = Np + lln[e]; ls[Np + lln[e] + 1]++; }
-        if (!carry_obs) { if (Ep) memcpy(ow, p->po_w.data(), (size_t)Ep * 8); if (El) memcpy(ow + Ep, p->lo_w.data(), (size_t)El * 8); }
+        if (!carry_obs) { if (Ep) memcpy(ow, w.po_w.data(), (size_t)Ep * 8); if (El) memcpy(ow + Ep, w.lo_w.data(), (size_t)El * 8); }
         for (int s = 0; s < L; ++s) ls[s + 1] += ls[s];
     }
     // ---- fused landmark-major passes: does the structure fit?  (decided for good once the chain maps exist, below) -----------------
@@ -972,16 +966,16 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
         for (int e = 0; e < E; ++e) { p->ob_pos[e] = cntk[ob_kf[e]]; cntk[ob_kf[e]] += (e < Ep) ? 1 : 2; }
     }
     // (a slid window's landmark estimates stay on the device: plba_slide_window left them in d_lm_carry, and the host copy is not formed)
-    const bool carry_all = (p->carry_pts || Np == 0) && (p->carry_lns || Nl == 0) && (p->carry_pts || p->carry_lns) && p->d_lm_carry.p && p->d_lm_carry.n >= (size_t)L * 6;
-    if ((p->carry_pts || p->carry_lns) && !carry_all) FAIL(p, PLBA_ERR_STATE, "after plba_slide_window set BOTH landmark arrays again (plba_set_points and plba_set_lines) or neither: the kept estimates live on the device");
+    const bool carry_all = (w.carry_pts || Np == 0) && (w.carry_lns || Nl == 0) && (w.carry_pts || w.carry_lns) && p->d_lm_carry.p && p->d_lm_carry.n >= (size_t)L * 6;
+    if ((w.carry_pts || w.carry_lns) && !carry_all) FAIL(p, PLBA_ERR_STATE, "after plba_slide_window set BOTH landmark arrays again (plba_set_points and plba_set_lines) or neither: the kept estimates live on the device");
     p->lm_fixed.assign(L, 0);
     if (!carry_all) {
         p->lm0.assign((size_t)L * 6, 0.0);
-        for (int i = 0; i < Np; ++i) memcpy(&p->lm0[(size_t)i * 6], &p->pts[(size_t)i * 3], 24);
-        for (int i = 0; i < Nl; ++i) memcpy(&p->lm0[(size_t)(Np + i) * 6], &p->lns[(size_t)i * 6], 48);
+        for (int i = 0; i < Np; ++i) memcpy(&p->lm0[(size_t)i * 6], &w.pts[(size_t)i * 3], 24);
+        for (int i = 0; i < Nl; ++i) memcpy(&p->lm0[(size_t)(Np + i) * 6], &w.lns[(size_t)i * 6], 48);
     }
-    for (int i = 0; i < Np; ++i) p->lm_fixed[i] = p->pt_fixed[i];
-    for (int i = 0; i < Nl; ++i) p->lm_fixed[Np + i] = p->ln_fixed[i];
+    for (int i = 0; i < Np; ++i) p->lm_fixed[i] = w.pt_fixed[i];
+    for (int i = 0; i < Nl; ++i) p->lm_fixed[Np + i] = w.ln_fixed[i];
     lap("index maps, slots");
     struct PoolJoin { ~PoolJoin() { HostPool::get().finish(); } } join_tables;      // (declared after the vectors the asynchronous fill reads: joined before they go)
     if (lm_cand) build_lm_groups(p, lm_start, ob_kf, LH);
@@ -1087,7 +1081,7 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
     size_t pr_nx = 0;
     {
         std::map<int, std::pair<int, int>> by_vid;
-        for (int k = 0; k < K; ++k) { by_vid[p->vid_pvr[k]] = {k, 0}; if (p->vid_bias[k] >= 0) by_vid[p->vid_bias[k]] = {k, 1}; }
+        for (int k = 0; k < K; ++k) { by_vid[w.vid_pvr[k]] = {k, 0}; if (w.vid_bias[k] >= 0) by_vid[w.vid_bias[k]] = {k, 1}; }
         int xo = 0;
         for (int i = 0; i < p->pr_nv; ++i) {
             auto it = by_vid.find(p->pr_vid[i]);
@@ -1103,10 +1097,10 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
     const double* pr_dev = p->prior_dev && p->pr_nv > 0 ? p->d_prd[p->prd_slot].p : nullptr;
     // ---- upload ----------------------------------------------------------------------------------------------------
     const size_t sysn = (size_t)(p->Ppad + TILE) * p->ld;
-    if (p->carry_kf) {      // a slid window: the kept keyframes' states never left the device (plba_slide_window)
+    if (w.carry_kf) {      // a slid window: the kept keyframes' states never left the device (plba_slide_window)
         if (p->d_kf_carry.n < (size_t)K * KF_STRIDE) FAIL(p, PLBA_ERR_STATE, "carried keyframe states do not fit the window (internal error)");
         for (DArr<double>* dst : {&p->d_kf[0], &p->d_kf[1], &p->d_kf_saved}) { HIPCK(p, dst->alloc((size_t)K * KF_STRIDE, false)); HIPCK(p, hipMemcpyAsync(dst->p, p->d_kf_carry.p, (size_t)K * KF_STRIDE * 8, hipMemcpyDeviceToDevice, p->stream)); }
-    } else { HIPCK(p, p->d_kf[0].upload(p->kf0)); HIPCK(p, p->d_kf[1].upload(p->kf0)); HIPCK(p, p->d_kf_saved.upload(p->kf0)); }
+    } else { HIPCK(p, p->d_kf[0].upload(w.kf0)); HIPCK(p, p->d_kf[1].upload(w.kf0)); HIPCK(p, p->d_kf_saved.upload(w.kf0)); }
     // the landmarks' three images (current, trial, saved): one pass through the staging area, two copies on the device (1.2 MB each at configs[2])
     p->lm_grouped = false;      // (slot order until the fused passes' groups are final, below)
     if (carry_all) {
@@ -1126,9 +1120,9 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
         if (p->carry_obs_pending) { p->d_po_uv.swap(p->d_po_uv_c); p->d_lo_l.swap(p->d_lo_l_c); p->d_ob_w.swap(p->d_ob_w_c); p->carry_obs_pending = false;
             p->d_po_uv_c.drop_batched(); p->d_lo_l_c.drop_batched(); p->d_ob_w_c.drop_batched(); }      // (the old buffers become the next slide's destination — unless they lived in the batch blocks, which start over now)
         if (p->d_po_uv.n < 2 * (size_t)Ep || p->d_lo_l.n < 3 * (size_t)El || p->d_ob_w.n < (size_t)E) FAIL(p, PLBA_ERR_STATE, "carried observation arrays do not fit the window (internal error)");
-    } else { HIPCK(p, p->d_po_uv.upload(p->po_uv)); HIPCK(p, p->d_lo_l.upload(p->lo_l)); HIPCK(p, p->d_ob_w.upload(ob_w)); }
+    } else { HIPCK(p, p->d_po_uv.upload(w.po_uv)); HIPCK(p, p->d_lo_l.upload(w.lo_l)); HIPCK(p, p->d_ob_w.upload(ob_w)); }
     HIPCK(p, p->d_ob_kf.upload(ob_kf)); HIPCK(p, p->d_ob_slot.upload(ob_slot)); HIPCK(p, p->d_lm_start.upload(lm_start));
-    HIPCK(p, p->d_level.upload(p->level)); HIPCK(p, p->d_lm_fixed.upload(p->lm_fixed));
+    HIPCK(p, p->d_level.upload(w.level)); HIPCK(p, p->d_lm_fixed.upload(p->lm_fixed));
     const size_t nrec = lm_cand ? 0 : ((size_t)Ep + 2 * (size_t)El) * EREC_UNIT;      // the fused passes write no record table (2 x 70 MB at configs[4])
     HIPCK(p, p->d_ob_chi2.alloc(E)); HIPCK(p, p->d_erec.alloc(nrec + EREC)); HIPCK(p, p->d_erec2.alloc(nrec + EREC)); HIPCK(p, p->d_depth.alloc(E));
     HIPCK(p, p->d_lm_active.alloc(L));
@@ -1172,8 +1166,8 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
     HIPCK(p, p->d_pair_i.upload(pair_i)); HIPCK(p, p->d_pair_j.upload(pair_j)); HIPCK(p, p->d_pair_start.upload(pair_start));
     if (ent_staged) { HIPCK(p, p->d_ent_pi.upload_staged(ent_ei, (size_t)nent)); HIPCK(p, p->d_ent_pj.upload_staged(ent_ej, (size_t)nent)); HIPCK(p, p->d_ent_slot.upload_staged(ent_slot, (size_t)nent)); }
     else { HIPCK(p, p->d_ent_pi.upload(ent_ei_v)); HIPCK(p, p->d_ent_pj.upload(ent_ej_v)); HIPCK(p, p->d_ent_slot.upload(ent_slot_v)); } HIPCK(p, p->d_ob_pos.upload(p->ob_pos));
-    HIPCK(p, p->d_imu_i.upload(p->imu_i)); HIPCK(p, p->d_imu_j.upload(p->imu_j)); HIPCK(p, p->d_imu_pre.upload(p->imu_pre));
-    HIPCK(p, p->d_imu_ipvr.upload(p->imu_ipvr)); HIPCK(p, p->d_imu_ibias.upload(p->imu_ibias));
+    HIPCK(p, p->d_imu_i.upload(w.imu_i)); HIPCK(p, p->d_imu_j.upload(w.imu_j)); HIPCK(p, p->d_imu_pre.upload(w.imu_pre));
+    HIPCK(p, p->d_imu_ipvr.upload(w.imu_ipvr)); HIPCK(p, p->d_imu_ibias.upload(w.imu_ibias));
     HIPCK(p, p->d_imu_err.alloc((size_t)M * 16)); HIPCK(p, p->d_imu_chi.alloc((size_t)M * 4));
     HIPCK(p, p->d_pr_kf.upload(pr_kf)); HIPCK(p, p->d_pr_isbias.upload(pr_isb)); HIPCK(p, p->d_pr_size.upload(p->pr_size));
     HIPCK(p, p->d_pr_idx.upload(p->pr_idx)); HIPCK(p, p->d_pr_x0off.upload(pr_x0off)); HIPCK(p, p->d_pr_off.upload(pr_off));
@@ -1197,11 +1191,11 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
     memset(&d, 0, sizeof d);
     d.K = K; d.Np = Np; d.Nl = Nl; d.L = L; d.Ep = Ep; d.El = El; d.E = E; d.M = M;
     d.P = p->P; d.Ppad = p->Ppad; d.ld = p->ld; d.npairs = (int)pair_i.size(); d.nent = (int)nent; d.nchunks = (int)ch_meta.size();
-    d.cam.fx = p->fx; d.cam.fy = p->fy; d.cam.cx = p->cx; d.cam.cy = p->cy;
-    M3 Rbc; for (int i = 0; i < 9; ++i) Rbc.a[i] = p->Rbc[i];
+    d.cam.fx = w.fx; d.cam.fy = w.fy; d.cam.cx = w.cx; d.cam.cy = w.cy;
+    M3 Rbc; for (int i = 0; i < 9; ++i) Rbc.a[i] = w.Rbc[i];
     d.cam.Rcb = transpose(Rbc);
-    d.cam.c0 = mul(d.cam.Rcb, v3(p->Pbc[0], p->Pbc[1], p->Pbc[2]));
-    d.gw = v3(p->gw[0], p->gw[1], p->gw[2]);
+    d.cam.c0 = mul(d.cam.Rcb, v3(w.Pbc[0], w.Pbc[1], w.Pbc[2]));
+    d.gw = v3(w.gw[0], w.gw[1], w.gw[2]);
     d.fix_q1 = p->opt.fix_line_position_jacobian;
     d.kf[0] = p->d_kf[0].p; d.kf[1] = p->d_kf[1].p; d.lm[0] = p->d_lm[0].p; d.lm[1] = p->d_lm[1].p;
     d.po_uv = p->d_po_uv.p; d.lo_l = p->d_lo_l.p; d.ob_w = p->d_ob_w.p; d.ob_kf = p->d_ob_kf.p; d.ob_slot = p->d_ob_slot.p;
@@ -1231,7 +1225,7 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
         for (int v : {K, M, p->pr_nv, p->pr_n, (int)lm_cand, p->world, p->rank, p->opt.chain_elim, p->opt.use_mfma, p->opt.factor_block, p->opt.factor_flow, p->opt.wide_steps, p->opt.band_solve,
                       p->opt.chain_seg, p->opt.twin_max_tiles, (int)(E > 300000), (int)p->lm_disable, p->P}) skey.push_back(v);
         skey.insert(skey.end(), p->off_pvr.begin(), p->off_pvr.end()); skey.insert(skey.end(), p->off_bias.begin(), p->off_bias.end());
-        skey.insert(skey.end(), p->imu_i.begin(), p->imu_i.end()); skey.insert(skey.end(), p->imu_j.begin(), p->imu_j.end());
+        skey.insert(skey.end(), w.imu_i.begin(), w.imu_i.end()); skey.insert(skey.end(), w.imu_j.begin(), w.imu_j.end());
         skey.insert(skey.end(), pr_kf.begin(), pr_kf.end()); skey.insert(skey.end(), pr_isb.begin(), pr_isb.end()); skey.insert(skey.end(), p->pr_size.begin(), p->pr_size.begin() + p->pr_nv); skey.insert(skey.end(), pr_off.begin(), pr_off.end());
         skey.insert(skey.end(), p->pr_idx.begin(), p->pr_idx.begin() + p->pr_nv);
         auto pack = [&](const std::vector<uint8_t>& v) { for (size_t i = 0; i < v.size(); i += 4) { int32_t w = 0; for (size_t j = i; j < std::min(i + 4, v.size()); ++j) w |= (int32_t)(v[j] & 0xFF) << (8 * (j - i)); skey.push_back(w); } };
@@ -1289,7 +1283,7 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
         bool ok = npos > 0;
         // block-tridiagonal only if every IMU edge joins neighbouring positions
         for (int m = 0; m < M && ok; ++m) {
-            const int bi = pos_of_kf[p->imu_i[m]], bj = pos_of_kf[p->imu_j[m]];
+            const int bi = pos_of_kf[w.imu_i[m]], bj = pos_of_kf[w.imu_j[m]];
             if (bi >= 0 && bj >= 0 && std::abs(bi - bj) > 1) ok = false;
         }
         // a marginalization prior couples the chain dims of its kept vertices with each other: those positions stay dense
@@ -1415,7 +1409,7 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
                         std::vector<int32_t> iloc((size_t)std::max(M, 1) * 4, -1);
                         bool iloc_ok = true;
                         for (int m = 0; m < M; ++m) {
-                            const int ki = p->imu_i[m], kj = p->imu_j[m];
+                            const int ki = w.imu_i[m], kj = w.imu_j[m];
                             const int gi = seg_of_kf[ki], gj = seg_of_kf[kj];
                             if (gi >= 0 && gj >= 0 && gi != gj) iloc_ok = false;      // (cannot happen: a separator sits between two segments)
                             iloc[4 * (size_t)m] = gi >= 0 ? gi : gj; iloc[4 * (size_t)m + 1] = desc_of_kf[ki]; iloc[4 * (size_t)m + 2] = desc_of_kf[kj];
@@ -1500,7 +1494,7 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
             for (int a = 0; a < n; ++a) { if (dims[a] < 0) continue; for (int b = 0; b < n; ++b) if (dims[b] >= 0) mark(dims[a] * ld + dims[b]); }
         };
         for (int m = 0; m < M; ++m) {   // IMU PVR edge over [PVR_i | PVR_j | Bias_i], bias edge over [Bias_i | Bias_j]
-            const int ki = p->imu_i[m], kj = p->imu_j[m];
+            const int ki = w.imu_i[m], kj = w.imu_j[m];
             int e1[24], e2[12];
             for (int c = 0; c < 9; ++c) e1[c] = p->off_pvr[ki] >= 0 ? p->off_pvr[ki] + c : -1;
             for (int c = 0; c < 9; ++c) e1[9 + c] = p->off_pvr[kj] >= 0 ? p->off_pvr[kj] + c : -1;
@@ -1658,7 +1652,7 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
             }
         }
         for (int m = 0; m < M; ++m) {   // IMU PVR edge over [PVR_i | PVR_j | Bias_i], bias edge over [Bias_i | Bias_j]
-            const int ki = p->imu_i[m], kj = p->imu_j[m];
+            const int ki = w.imu_i[m], kj = w.imu_j[m];
             std::vector<int> e1, e2;
             for (int c = 0; c < 9; ++c) { e1.push_back(p->off_pvr[ki] >= 0 ? p->off_pvr[ki] + c : -1); }
             for (int c = 0; c < 9; ++c) { e1.push_back(p->off_pvr[kj] >= 0 ? p->off_pvr[kj] + c : -1); }
@@ -2399,30 +2393,30 @@ int plba_recompute_errors(plba_problem* p) {
 int plba_set_levels(plba_problem* p, plba_edge_kind kind, const uint8_t* level) {
     if (!p || !level) return PLBA_ERR_INVALID;
     if (kind != PLBA_EDGE_POINT && kind != PLBA_EDGE_LINE) FAIL(p, PLBA_ERR_INVALID, "levels only for point/line edges");
-    const int E = p->Ep + p->El;
-    if ((int)p->level.size() != E) p->level.assign(E, 0);
+    const int E = p->win.Ep + p->win.El;
+    if ((int)p->win.level.size() != E) p->win.level.assign(E, 0);
     if (!p->dirty) {   // device copy may have been changed by gate_outliers: refresh the host mirror first
         HIPCK(p, hipSetDevice(p->device));
         HIPCK(p, plba_stream_wait(p, p->stream));
-        if (E) HIPCK(p, plba_d2h(p, p->level.data(), p->d_level.p, E));
+        if (E) HIPCK(p, plba_d2h(p, p->win.level.data(), p->d_level.p, E));
     }
-    if (kind == PLBA_EDGE_POINT) memcpy(p->level.data(), level, p->Ep);
-    else memcpy(p->level.data() + p->Ep, level, p->El);
-    if (!p->dirty && E) { HIPCK(p, plba_h2d(p, p->d_level.p, p->level.data(), E)); if (p->lm_ok) launch_lm_level_sync(p->dv, p->lv, p->stream); }
+    if (kind == PLBA_EDGE_POINT) memcpy(p->win.level.data(), level, p->win.Ep);
+    else memcpy(p->win.level.data() + p->win.Ep, level, p->win.El);
+    if (!p->dirty && E) { HIPCK(p, plba_h2d(p, p->d_level.p, p->win.level.data(), E)); if (p->lm_ok) launch_lm_level_sync(p->dv, p->lv, p->stream); }
     return PLBA_OK;
 }
 int plba_get_levels(plba_problem* p, plba_edge_kind kind, uint8_t* level) {
     if (!p || !level) return PLBA_ERR_INVALID;
     if (kind != PLBA_EDGE_POINT && kind != PLBA_EDGE_LINE) return PLBA_ERR_INVALID;
-    const int E = p->Ep + p->El;
-    if ((int)p->level.size() != E) p->level.assign(E, 0);
+    const int E = p->win.Ep + p->win.El;
+    if ((int)p->win.level.size() != E) p->win.level.assign(E, 0);
     if (!p->dirty && E) {
         HIPCK(p, hipSetDevice(p->device));
         HIPCK(p, plba_stream_wait(p, p->stream));
-        HIPCK(p, plba_d2h(p, p->level.data(), p->d_level.p, E));
+        HIPCK(p, plba_d2h(p, p->win.level.data(), p->d_level.p, E));
     }
-    if (kind == PLBA_EDGE_POINT) memcpy(level, p->level.data(), p->Ep);
-    else memcpy(level, p->level.data() + p->Ep, p->El);
+    if (kind == PLBA_EDGE_POINT) memcpy(level, p->win.level.data(), p->win.Ep);
+    else memcpy(level, p->win.level.data() + p->win.Ep, p->win.El);
     return PLBA_OK;
 }
 
@@ -2452,7 +2446,7 @@ int plba_cull_observations(plba_problem* p, double thresh, uint8_t* bad_point, u
     if (rc) return rc;
     HIPCK(p, hipSetDevice(p->device));
     const DevBuf& d = p->dv;
-    const int E = p->Ep + p->El;
+    const int E = p->win.Ep + p->win.El;
     std::vector<uint8_t> bad((size_t)std::max(E, 1), 0);
     if (E) {
         lm_chi_sync(p);
@@ -2461,10 +2455,10 @@ int plba_cull_observations(plba_problem* p, double thresh, uint8_t* bad_point, u
         HIPCK(p, plba_d2h(p, bad.data(), p->d_depth.p, (size_t)E));
     }
     int np = 0, nl = 0;
-    for (int e = 0; e < p->Ep; ++e) np += bad[e];
-    for (int e = 0; e < p->El; ++e) nl += bad[p->Ep + e];
-    if (bad_point && p->Ep) memcpy(bad_point, bad.data(), (size_t)p->Ep);
-    if (bad_line && p->El) memcpy(bad_line, bad.data() + p->Ep, (size_t)p->El);
+    for (int e = 0; e < p->win.Ep; ++e) np += bad[e];
+    for (int e = 0; e < p->win.El; ++e) nl += bad[p->win.Ep + e];
+    if (bad_point && p->win.Ep) memcpy(bad_point, bad.data(), (size_t)p->win.Ep);
+    if (bad_line && p->win.El) memcpy(bad_line, bad.data() + p->win.Ep, (size_t)p->win.El);
     if (np_out) *np_out = np;
     if (nl_out) *nl_out = nl;
     return np + nl;
@@ -2477,16 +2471,16 @@ int plba_get_edge_chi2(plba_problem* p, plba_edge_kind kind, double* chi2, uint8
     HIPCK(p, hipSetDevice(p->device));
     const DevBuf& d = p->dv;
     if (kind == PLBA_EDGE_POINT || kind == PLBA_EDGE_LINE) {
-        const int o = kind == PLBA_EDGE_POINT ? 0 : p->Ep, n = kind == PLBA_EDGE_POINT ? p->Ep : p->El;
+        const int o = kind == PLBA_EDGE_POINT ? 0 : p->win.Ep, n = kind == PLBA_EDGE_POINT ? p->win.Ep : p->win.El;
         // (both kernels queued before the first copy waits: one device round trip per call instead of three)
         if (chi2 && n) lm_chi_sync(p);
         if (dpos && n) launch_depth(d, p->cur, p->d_depth.p, p->stream);
         if (chi2 && n) HIPCK(p, plba_d2h(p, chi2, d.ob_chi2 + o, (size_t)n * 8));
         if (dpos && n) HIPCK(p, plba_d2h(p, dpos, p->d_depth.p + o, n));
     } else if (kind == PLBA_EDGE_IMU_PVR || kind == PLBA_EDGE_IMU_BIAS) {
-        std::vector<double> c((size_t)p->M * 4);
-        if (p->M) HIPCK(p, plba_d2h(p, c.data(), d.imu_chi, c.size() * 8));
-        for (int m = 0; m < p->M; ++m) { if (chi2) chi2[m] = c[(size_t)m * 4 + (kind == PLBA_EDGE_IMU_PVR ? 0 : 1)]; if (dpos) dpos[m] = 1; }
+        std::vector<double> c((size_t)p->win.M * 4);
+        if (p->win.M) HIPCK(p, plba_d2h(p, c.data(), d.imu_chi, c.size() * 8));
+        for (int m = 0; m < p->win.M; ++m) { if (chi2) chi2[m] = c[(size_t)m * 4 + (kind == PLBA_EDGE_IMU_PVR ? 0 : 1)]; if (dpos) dpos[m] = 1; }
     } else if (kind == PLBA_EDGE_PRIOR) {
         double c = 0.0;
         if (p->pr_nv) HIPCK(p, plba_d2h(p, &c, d.pr_chi, 8));
@@ -2521,7 +2515,7 @@ __global__ void k_lm_pack(const double* __restrict__ lm, const int32_t* __restri
 static int get_results(plba_problem* p, int what, double* xyz, double* lines, double* P3, double* V3, double* q4, double* dbg3, double* dba3) {
     int rc = prepare(p);
     if (rc) return rc;
-    const size_t np3 = 3 * (size_t)p->Np, nl6 = 6 * (size_t)p->Nl, nkf = (size_t)p->K * KF_STRIDE, tot = np3 + nl6 + nkf;
+    const size_t np3 = 3 * (size_t)p->win.Np, nl6 = 6 * (size_t)p->win.Nl, nkf = (size_t)p->win.K * KF_STRIDE, tot = np3 + nl6 + nkf;
     std::vector<double>& h = p->res_lm;      // [points packed | lines packed | keyframe states] of epoch res_lm_epoch
     const double* src = nullptr;
     if (!(p->res_lm_epoch == p->state_epoch && h.size() == tot)) {
@@ -2530,7 +2524,7 @@ static int get_results(plba_problem* p, int what, double* xyz, double* lines, do
         h.resize(tot);
         if (tot) {
             HIPCK(p, p->d_lm_pack.alloc(tot, false));
-            hipLaunchKernelGGL(k_lm_pack, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, p->stream, p->dv.lm[p->cur], p->lm_grouped ? p->d_lm_pos.p : nullptr, p->Np, p->Nl,
+            hipLaunchKernelGGL(k_lm_pack, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, p->stream, p->dv.lm[p->cur], p->lm_grouped ? p->d_lm_pos.p : nullptr, p->win.Np, p->win.Nl,
                                p->dv.kf[p->cur], (int)nkf, p->d_lm_pack.p);
             HIPCK(p, hipGetLastError());
             if (st && st->base && tot * 8 <= st->xfer_cap()) {
@@ -2546,7 +2540,7 @@ static int get_results(plba_problem* p, int what, double* xyz, double* lines, do
     if (what == 1 && xyz && np3) memcpy(xyz, src, np3 * 8);
     if (what == 2 && lines && nl6) memcpy(lines, src + np3, nl6 * 8);
     if (what == 0) {
-        for (int k = 0; k < p->K; ++k) {
+        for (int k = 0; k < p->win.K; ++k) {
             const double* s = src + np3 + nl6 + (size_t)k * KF_STRIDE;
             if (P3) memcpy(P3 + 3 * k, s, 24);
             if (V3) memcpy(V3 + 3 * k, s + 3, 24);
@@ -2574,7 +2568,7 @@ int plba_save_state(plba_problem* p) {
     int rc = prepare(p);
     if (rc) return rc;
     HIPCK(p, hipSetDevice(p->device));
-    HIPCK(p, hipMemcpyAsync(p->d_kf_saved.p, p->dv.kf[p->cur], (size_t)p->K * KF_STRIDE * 8, hipMemcpyDeviceToDevice, p->stream));
+    HIPCK(p, hipMemcpyAsync(p->d_kf_saved.p, p->dv.kf[p->cur], (size_t)p->win.K * KF_STRIDE * 8, hipMemcpyDeviceToDevice, p->stream));
     if (p->L) HIPCK(p, hipMemcpyAsync(p->d_lm_saved.p, p->dv.lm[p->cur], (size_t)p->L * 6 * 8, hipMemcpyDeviceToDevice, p->stream));
     return PLBA_OK;
 }
@@ -2584,7 +2578,7 @@ int plba_restore_state(plba_problem* p) {
     if (rc) return rc;
     HIPCK(p, hipSetDevice(p->device));
     ++p->state_epoch;
-    HIPCK(p, hipMemcpyAsync(p->dv.kf[p->cur], p->d_kf_saved.p, (size_t)p->K * KF_STRIDE * 8, hipMemcpyDeviceToDevice, p->stream));
+    HIPCK(p, hipMemcpyAsync(p->dv.kf[p->cur], p->d_kf_saved.p, (size_t)p->win.K * KF_STRIDE * 8, hipMemcpyDeviceToDevice, p->stream));
     if (p->L) HIPCK(p, hipMemcpyAsync(p->dv.lm[p->cur], p->d_lm_saved.p, (size_t)p->L * 6 * 8, hipMemcpyDeviceToDevice, p->stream));
     return PLBA_OK;
 }
@@ -2620,114 +2614,36 @@ __global__ void k_obs_carry_gather(const double* __restrict__ po_uv0, const doub
 }
 int plba_get_sizes(const plba_problem* p, int32_t* out6) {
     if (!p || !out6) return PLBA_ERR_INVALID;
-    out6[0] = p->K; out6[1] = p->Np; out6[2] = p->Nl; out6[3] = p->Ep; out6[4] = p->El; out6[5] = p->M;
+    out6[0] = p->win.K; out6[1] = p->win.Np; out6[2] = p->win.Nl; out6[3] = p->win.Ep; out6[4] = p->win.El; out6[5] = p->win.M;
     return PLBA_OK;
 }
+// Three parts.  PLAN (plba_window.h, pure host code): every check, the keep / drop maps, the merged lists, and the complete next window in
+// p->win_next — the resident one is read through a const reference.  STAGE: everything that can return a device error; it writes only
+// the slide's own buffers (d_kf_carry, d_lm_carry(_src), d_slide_*, d_obs_carry_src, the d_*_c arrays), none of which a window that is not
+// dirty reads.  COMMIT: the two windows are swapped.  After the first write to p->win there is no HIP call and no return but the last
+// one: whatever the call returns before that, the handle still holds the previous window, not dirty and usable.
 int plba_slide_window(plba_problem* p, const plba_slide* s, int32_t* point_map, int32_t* line_map) {
     if (!p || !s) return PLBA_ERR_INVALID;
     if (p->world > 1) FAIL(p, PLBA_ERR_STATE, "plba_slide_window: a sharded problem takes a fresh upload");
-    if (p->dirty || !p->K) FAIL(p, PLBA_ERR_STATE, "plba_slide_window: no window is resident on the device (upload one and optimize it first)");
-    const int K0 = p->K, Np0 = p->Np, Nl0 = p->Nl, Ep0 = p->Ep, El0 = p->El, M0 = p->M, nd = s->n_drop;
-    if (nd < 0 || nd >= K0 || s->K_add < 0 || s->M_add < 0 || s->Np_add < 0 || s->Nl_add < 0 || s->Ep_add < 0 || s->El_add < 0) FAIL(p, PLBA_ERR_INVALID, "plba_slide_window: counts out of range (n_drop %d of %d keyframes)", nd, K0);
-    const int K1 = K0 - nd + s->K_add;
-    if (s->K_add && (!s->vid_pvr || !s->P3 || !s->V3 || !s->q_xyzw4)) return PLBA_ERR_INVALID;
-    if ((s->M_add && (!s->imu_kf_i || !s->imu_kf_j || !s->preint142 || !s->info_pvr81 || !s->info_bias36)) || (s->Np_add && !s->xyz3) || (s->Nl_add && !s->sPeP6) ||
-        (s->Ep_add && (!s->po_pt || !s->po_kf || !s->uv2)) || (s->El_add && (!s->lo_ln || !s->lo_kf || !s->l3))) return PLBA_ERR_INVALID;
-    for (int k = 0; k < s->K_add; ++k) {
-        const int prev = k ? s->vid_pvr[k - 1] : p->vid_pvr[K0 - 1];
-        if (s->vid_pvr[k] <= prev) FAIL(p, PLBA_ERR_INVALID, "keyframe vertex ids must be ascending");
-    }
-    if (!all_finite(s->P3, 3 * (size_t)s->K_add) || !all_finite(s->V3, 3 * (size_t)s->K_add) || !all_finite(s->q_xyzw4, 4 * (size_t)s->K_add)) FAIL(p, PLBA_ERR_NUMERIC, "non-finite keyframe state");
-    if (!all_finite(s->xyz3, 3 * (size_t)s->Np_add) || !all_finite(s->sPeP6, 6 * (size_t)s->Nl_add) || !all_finite(s->uv2, 2 * (size_t)s->Ep_add) || !all_finite(s->l3, 3 * (size_t)s->El_add)) FAIL(p, PLBA_ERR_NUMERIC, "non-finite landmark or observation");
-    if (!all_finite(s->preint142, 142 * (size_t)s->M_add) || !all_finite(s->info_pvr81, 81 * (size_t)s->M_add)) FAIL(p, PLBA_ERR_NUMERIC, "non-finite IMU edge");
-    HIPCK(p, hipSetDevice(p->device));
+    if (p->dirty || !p->win.K) FAIL(p, PLBA_ERR_STATE, "plba_slide_window: no window is resident on the device (upload one and optimize it first)");
     const bool stime = (p->opt.diag & PLBA_DIAG_TIMING) != 0;
     auto st0 = std::chrono::steady_clock::now();
     auto slap = [&](const char* what) { if (!stime) return; auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[slide] %-30s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - st0).count()); st0 = t; };
-    // ---- which landmarks / observations stay -------------------------------------------------------------------------------------
-    std::vector<int32_t> pmap(Np0), lmap(Nl0);
-    std::vector<uint8_t> pdrop(Np0, 0), ldrop(Nl0, 0);
-    if (s->drop_point) for (int i = 0; i < Np0; ++i) pdrop[i] = s->drop_point[i] != 0;
-    if (s->drop_line) for (int i = 0; i < Nl0; ++i) ldrop[i] = s->drop_line[i] != 0;
-    for (int e = 0; e < Ep0; ++e) if (p->po_kf[e] < nd) pdrop[p->po_pt[e]] = 1;
-    for (int e = 0; e < El0; ++e) if (p->lo_kf[e] < nd) ldrop[p->lo_ln[e]] = 1;
-    int Np1 = 0, Nl1 = 0;
-    for (int i = 0; i < Np0; ++i) pmap[i] = pdrop[i] ? -1 : Np1++;
-    for (int i = 0; i < Nl0; ++i) lmap[i] = ldrop[i] ? -1 : Nl1++;
-    const int Npk = Np1, Nlk = Nl1;      // kept
-    Np1 += s->Np_add; Nl1 += s->Nl_add;
-    // added observations: landmark index before the slide (must stay) or N_before + i; keyframes in the new numbering
-    auto check_add = [&](int E, const int32_t* lm, const int32_t* kf, int N0, int Nadd, const std::vector<int32_t>& map, const char* what) -> int {
-        for (int e = 0; e < E; ++e) {
-            if (lm[e] < 0 || lm[e] >= N0 + Nadd) FAIL(p, PLBA_ERR_INVALID, "added %s observation %d: landmark index %d out of range", what, e, lm[e]);
-            if (lm[e] < N0 && map[lm[e]] < 0) FAIL(p, PLBA_ERR_INVALID, "added %s observation %d: landmark %d leaves the window with this slide", what, e, lm[e]);
-            if (kf[e] < 0 || kf[e] >= K1) FAIL(p, PLBA_ERR_INVALID, "added %s observation %d: keyframe index %d out of range (new numbering, %d keyframes)", what, e, kf[e], K1);
-            if (e && lm[e] < lm[e - 1]) FAIL(p, PLBA_ERR_INVALID, "added %s observations must be sorted by landmark", what);
-        }
-        return PLBA_OK;
-    };
-    if (int rc = check_add(s->Ep_add, s->po_pt, s->po_kf, Np0, s->Np_add, pmap, "point")) return rc;
-    if (int rc = check_add(s->El_add, s->lo_ln, s->lo_kf, Nl0, s->Nl_add, lmap, "line")) return rc;
-    for (int m = 0; m < s->M_add; ++m) if (s->imu_kf_i[m] < 0 || s->imu_kf_i[m] >= K1 || s->imu_kf_j[m] < 0 || s->imu_kf_j[m] >= K1) FAIL(p, PLBA_ERR_INVALID, "added imu edge %d: keyframe index (new numbering)", m);
-    // ---- host copy of the graph: observations compacted, shifted and merged landmark by landmark (into temporaries: nothing of the problem
-    // is touched before every check has passed) ----------------------------------------------------------------------------------------
-    // (round 5: only the integer lists — landmark and keyframe of every observation — are rebuilt on the host; `src` says where each new
-    // observation's measurement and weight come from: an index into the OLD device arrays, or -(1 + a) for the a-th added one)
-    struct ObsList { std::vector<int32_t>& lm; std::vector<int32_t>& kf; std::vector<int32_t>& src; };
-    // The old list is landmark-major and so is the added one: the merged list is the old one with the dropped landmarks' stretches cut
-    // out and each added run spliced in behind its landmark's last old observation.  Between two splice points the old observations are
-    // copied in one tight loop (new landmark index through the map, keyframe index shifted, source = old position); only a landmark that
-    // RECEIVES observations is checked for a keyframe seeing it twice (the old ones were checked when they were uploaded).
-    auto merge = [&](int N0, int Nadd, int E0, int Eadd, const std::vector<int32_t>& map, int nkept, const std::vector<int32_t>& ob_lm, const std::vector<int32_t>& ob_kf,
-                     const uint8_t* drop_obs, const int32_t* a_lm, const int32_t* a_kf, ObsList& out) -> int {
-        out.lm.resize((size_t)E0 + Eadd); out.kf.resize((size_t)E0 + Eadd); out.src.resize((size_t)E0 + Eadd);
-        int32_t* olm = out.lm.data(); int32_t* okf = out.kf.data(); int32_t* osrc = out.src.data();
-        const int32_t* mp = map.data(); const int32_t* il = ob_lm.data(); const int32_t* ik = ob_kf.data();
-        size_t n = 0;
-        auto copy_old = [&](int e0, int e1) {      // old observations [e0, e1)
-            if (!drop_obs) { for (int e = e0; e < e1; ++e) { const int nl = mp[il[e]]; olm[n] = nl; okf[n] = ik[e] - nd; osrc[n] = e; n += nl >= 0; } }
-            else for (int e = e0; e < e1; ++e) { const int nl = mp[il[e]]; olm[n] = nl; okf[n] = ik[e] - nd; osrc[n] = e; n += (nl >= 0) & !drop_obs[e]; }
-        };
-        int e = 0, a = 0;
-        while (a < Eadd) {
-            const int l = a_lm[a];
-            int a1 = a;
-            while (a1 < Eadd && a_lm[a1] == l) ++a1;
-            const int nl = l < N0 ? mp[l] : nkept + (l - N0);
-            // old observations up to and including landmark l's (none for an added landmark: those come after every old one)
-            const int e1 = l < N0 ? (int)(std::upper_bound(il + e, il + E0, l) - il) : E0;
-            const size_t before = n;
-            copy_old(e, e1);
-            e = e1;
-            size_t first = n;      // where landmark l's own (kept) observations start in the output
-            while (first > before && olm[first - 1] == nl) --first;
-            for (int q = a; q < a1; ++q) { olm[n] = nl; okf[n] = a_kf[q]; osrc[n] = -(1 + q); ++n; }
-            for (size_t x = first; x < n; ++x) for (size_t y = std::max(x + 1, n - (size_t)(a1 - a)); y < n; ++y)
-                if (okf[y] == okf[x]) FAIL(p, PLBA_ERR_INVALID, "landmark %d observed twice by keyframe %d", nl, okf[x]);
-            a = a1;
-        }
-        copy_old(e, E0);
-        out.lm.resize(n); out.kf.resize(n); out.src.resize(n);
-        return PLBA_OK;
-    };
-    ObsList npo{p->scr_lm[0], p->scr_kf[0], p->scr_src[0]}, nlo{p->scr_lm[1], p->scr_kf[1], p->scr_src[1]};
-    if (int rc = merge(Np0, s->Np_add, Ep0, s->Ep_add, pmap, Npk, p->po_pt, p->po_kf, s->drop_point_obs, s->po_pt, s->po_kf, npo)) return rc;
-    if (int rc = merge(Nl0, s->Nl_add, El0, s->El_add, lmap, Nlk, p->lo_ln, p->lo_kf, s->drop_line_obs, s->lo_ln, s->lo_kf, nlo)) return rc;
-    slap("observation lists merged");
-    for (int m = 0; m < s->M_add; ++m) {      // bias vertices of the added edges' keyframes (new numbering: kept ones shifted, added ones from the call)
-        for (int kk : {s->imu_kf_i[m], s->imu_kf_j[m]}) {
-            const int vb = kk < K0 - nd ? p->vid_bias[kk + nd] : (s->vid_bias ? s->vid_bias[kk - (K0 - nd)] : -1);
-            if (vb < 0) FAIL(p, PLBA_ERR_INVALID, "added imu edge %d: keyframe without bias vertex", m);
-        }
-    }
-    // ---- keyframes: the kept ones' current states are copied ON THE DEVICE behind the added ones' upload (round 5: they came back to
-    // the host first — a blocking read-back per slide) -------------------------------------------------------------------------------------
+    // ---- plan ----------------------------------------------------------------------------------------------------------------------------
+    const Window& w0 = p->win;
+    const Window& w1 = p->win_next;
+    const SlidePlan& pl = p->slide;
+    if (int rc = slide_plan(w0, *s, p->win_next, p->slide, p->err, sizeof p->err)) return rc;
+    slap("plan (checks, lists, host window)");
+    // ---- stage ---------------------------------------------------------------------------------------------------------------------------
+    HIPCK(p, hipSetDevice(p->device));
+    const int nd = s->n_drop, Kk = w0.K - nd, L1 = w1.Np + w1.Nl, E1 = w1.Ep + w1.El;
     // the slide's uploads go through a pinned area of their own (sized here; kept with the cached context): the copies and the gather
     // kernels are queued and the slide returns WITHOUT waiting for them — prepare() re-uses the general staging area at once, and they
-    // overlap its host work.  (No room / no pinned memory: the general area, and one wait at the slide's end.)
+    // overlap its host work.  (No room / no pinned memory: the general area, and one wait at the stage's end.)
     bool own_stage = false;
     if (p->have_ctx) {
-        const size_t need = ((size_t)(Np1 + Nl1) * 4 + (size_t)(s->Np_add + s->Nl_add) * 48 + ((size_t)Ep0 + El0 + s->Ep_add + s->El_add) * 4 + (size_t)s->Ep_add * 24 + (size_t)s->El_add * 32 +
+        const size_t need = ((size_t)L1 * 4 + (size_t)(s->Np_add + s->Nl_add) * 48 + ((size_t)w0.Ep + w0.El + s->Ep_add + s->El_add) * 4 + (size_t)s->Ep_add * 24 + (size_t)s->El_add * 32 +
                              (size_t)s->K_add * KF_STRIDE * 8 + 8 * 256 + StageArea::XFER) * 5 / 4;
         if (!p->ctx.slide_stage) p->ctx.slide_stage = new StageArea;
         StageArea* ss = p->ctx.slide_stage;
@@ -2738,115 +2654,37 @@ int plba_slide_window(plba_problem* p, const plba_slide* s, int32_t* point_map, 
         }
         own_stage = ss->base != nullptr && ss->cap >= need;
     }
+    // (a queued upload that found no staging room reads its host vector until the wait below: the plan's vectors are the problem's)
     DArrStreamScope staged(p->stream, own_stage ? p->ctx.slide_stage : (p->have_ctx ? p->ctx.stage : nullptr));
-    std::vector<double> kf_add((size_t)std::max(s->K_add, 1) * KF_STRIDE, 0.0);
-    DArr<double>& d_kf_add = p->d_slide_kf; DArr<double>& dadd_lm = p->d_slide_lm; DArr<double>& dadd_ob = p->d_slide_ob;
-    std::vector<int32_t> h_src_lm, h_src_ob;      // (function scope: a queued upload that found no staging room reads the host vector until the wait)
-    std::vector<double> h_add_lm, h_add_ob;
-    {
-        std::vector<int32_t> vp(K1), vb(K1, -1);
-        std::vector<uint8_t> fp(K1, 0), fb(K1, 0);
-        for (int k = nd; k < K0; ++k) { vp[k - nd] = p->vid_pvr[k]; vb[k - nd] = p->vid_bias[k]; fp[k - nd] = p->fix_pvr[k]; fb[k - nd] = p->fix_bias[k]; }
-        for (int k = 0; k < s->K_add; ++k) {
-            double* o = &kf_add[(size_t)k * KF_STRIDE];
-            memcpy(o, s->P3 + 3 * k, 24); memcpy(o + 3, s->V3 + 3 * k, 24); memcpy(o + 6, s->q_xyzw4 + 4 * k, 32);
-            if (s->bg3) memcpy(o + 10, s->bg3 + 3 * k, 24);
-            if (s->ba3) memcpy(o + 13, s->ba3 + 3 * k, 24);
-            if (s->dbg3) memcpy(o + 16, s->dbg3 + 3 * k, 24);
-            if (s->dba3) memcpy(o + 19, s->dba3 + 3 * k, 24);
-            vp[K0 - nd + k] = s->vid_pvr[k]; vb[K0 - nd + k] = s->vid_bias ? s->vid_bias[k] : -1;
-        }
-        if (s->fixed_pvr) for (int k = 0; k < K1; ++k) fp[k] = s->fixed_pvr[k];
-        if (s->fixed_bias) for (int k = 0; k < K1; ++k) fb[k] = s->fixed_bias[k];
-        HIPCK(p, p->d_kf_carry.alloc((size_t)K1 * KF_STRIDE, false));
-        HIPCK(p, hipMemcpyAsync(p->d_kf_carry.p, p->dv.kf[p->cur] + (size_t)nd * KF_STRIDE, (size_t)(K0 - nd) * KF_STRIDE * 8, hipMemcpyDeviceToDevice, p->stream));
-        if (s->K_add) { HIPCK(p, d_kf_add.upload(kf_add)); HIPCK(p, hipMemcpyAsync(p->d_kf_carry.p + (size_t)(K0 - nd) * KF_STRIDE, d_kf_add.p, (size_t)s->K_add * KF_STRIDE * 8, hipMemcpyDeviceToDevice, p->stream)); }
-        p->kf0.assign((size_t)K1 * KF_STRIDE, 0.0);      // (stale: carry_kf)
-        p->carry_kf = true;
-        p->vid_pvr.swap(vp); p->vid_bias.swap(vb); p->fix_pvr.swap(fp); p->fix_bias.swap(fb);
-    }
+    // keyframes: the kept ones' current states are copied ON THE DEVICE behind the added ones' upload
+    HIPCK(p, p->d_kf_carry.alloc((size_t)w1.K * KF_STRIDE, false));
+    HIPCK(p, hipMemcpyAsync(p->d_kf_carry.p, p->dv.kf[p->cur] + (size_t)nd * KF_STRIDE, (size_t)Kk * KF_STRIDE * 8, hipMemcpyDeviceToDevice, p->stream));
+    if (s->K_add) { HIPCK(p, p->d_slide_kf.upload(pl.kf_add)); HIPCK(p, hipMemcpyAsync(p->d_kf_carry.p + (size_t)Kk * KF_STRIDE, p->d_slide_kf.p, (size_t)s->K_add * KF_STRIDE * 8, hipMemcpyDeviceToDevice, p->stream)); }
     slap("keyframes");
-    // ---- landmarks: the new array is gathered ON THE DEVICE from the current estimates; only the added ones go up ----------------------------
-    {
-        const int L1 = Np1 + Nl1;
-        std::vector<int32_t>& src = h_src_lm; src.assign(std::max(L1, 1), 0);
-        for (int i = 0; i < Np0; ++i) if (pmap[i] >= 0) src[pmap[i]] = i;
-        for (int i = 0; i < s->Np_add; ++i) src[Npk + i] = -(1 + i);
-        for (int i = 0; i < Nl0; ++i) if (lmap[i] >= 0) src[Np1 + lmap[i]] = Np0 + i;
-        for (int i = 0; i < s->Nl_add; ++i) src[Np1 + Nlk + i] = -(1 + s->Np_add + i);
-        std::vector<double>& add = h_add_lm; add.assign((size_t)std::max(s->Np_add + s->Nl_add, 1) * 6, 0.0);
-        for (int i = 0; i < s->Np_add; ++i) memcpy(&add[(size_t)i * 6], s->xyz3 + 3 * (size_t)i, 24);
-        for (int i = 0; i < s->Nl_add; ++i) memcpy(&add[(size_t)(s->Np_add + i) * 6], s->sPeP6 + 6 * (size_t)i, 48);
-        // (uploads go through the pinned staging area — copied there at once, so `src` / `add` may end with this block; the device buffers
-        // dadd_* live until the slide's one wait at its end)
-        HIPCK(p, p->d_lm_carry_src.upload(src)); HIPCK(p, dadd_lm.upload(add));
-        HIPCK(p, p->d_lm_carry.alloc(std::max<size_t>((size_t)L1 * 6, 1), false));
-        if (L1) hipLaunchKernelGGL(k_lm_carry_gather, dim3((L1 * 6 + 255) / 256), dim3(256), 0, p->stream, p->dv.lm[p->cur], p->lm_grouped ? p->d_lm_pos.p : nullptr, dadd_lm.p, p->d_lm_carry_src.p, Np1, L1, p->d_lm_carry.p);
-        HIPCK(p, hipGetLastError());
-        p->carry_pts = true; p->carry_lns = true;
-    }
+    // landmarks: the new array is gathered ON THE DEVICE from the current estimates; only the added ones go up
+    HIPCK(p, p->d_lm_carry_src.upload(pl.src_lm)); HIPCK(p, p->d_slide_lm.upload(pl.add_lm));
+    HIPCK(p, p->d_lm_carry.alloc(std::max<size_t>((size_t)L1 * 6, 1), false));
+    if (L1) hipLaunchKernelGGL(k_lm_carry_gather, dim3((L1 * 6 + 255) / 256), dim3(256), 0, p->stream, p->dv.lm[p->cur], p->lm_grouped ? p->d_lm_pos.p : nullptr, p->d_slide_lm.p, p->d_lm_carry_src.p, w1.Np, L1, p->d_lm_carry.p);
+    HIPCK(p, hipGetLastError());
     slap("landmark carry");
-    // ---- measurements and weights: gathered on the device from the old landmark-major arrays + the added observations -----------------------
+    // measurements and weights: gathered on the device from the old landmark-major arrays + the added observations
     {
-        const int Ep1 = (int)npo.lm.size(), El1 = (int)nlo.lm.size(), E1 = Ep1 + El1;
-        std::vector<int32_t>& src = h_src_ob; src.resize(std::max(E1, 1));
-        if (Ep1) memcpy(src.data(), npo.src.data(), (size_t)Ep1 * 4);
-        if (El1) memcpy(src.data() + Ep1, nlo.src.data(), (size_t)El1 * 4);
-        std::vector<double>& add = h_add_ob; add.resize(std::max<size_t>(3 * (size_t)s->Ep_add + 4 * (size_t)s->El_add, 1));      // [uv (2 Ep_add) | w (Ep_add) | l (3 El_add) | w (El_add)]
-        double* a_uv = add.data(); double* a_wp = a_uv + 2 * (size_t)s->Ep_add; double* a_l = a_wp + s->Ep_add; double* a_wl = a_l + 3 * (size_t)s->El_add;
-        if (s->Ep_add) memcpy(a_uv, s->uv2, 16 * (size_t)s->Ep_add);
-        for (int e = 0; e < s->Ep_add; ++e) a_wp[e] = s->po_inv_sigma2 ? (double)(float)s->po_inv_sigma2[e] : 1.0;      // const float& invSigma2 (mapHandler.cpp:5340)
-        if (s->El_add) memcpy(a_l, s->l3, 24 * (size_t)s->El_add);
-        for (int e = 0; e < s->El_add; ++e) a_wl[e] = s->lo_inv_sigma2 ? (double)(float)s->lo_inv_sigma2[e] : 1.0;
-        DArr<double>& dadd = dadd_ob;
-        HIPCK(p, p->d_obs_carry_src.upload(src)); HIPCK(p, dadd.upload(add));
-        HIPCK(p, p->d_po_uv_c.alloc(std::max<size_t>(2 * (size_t)Ep1, 1), false)); HIPCK(p, p->d_lo_l_c.alloc(std::max<size_t>(3 * (size_t)El1, 1), false)); HIPCK(p, p->d_ob_w_c.alloc(std::max<size_t>((size_t)E1, 1), false));
+        DArr<double>& dadd = p->d_slide_ob;
+        HIPCK(p, p->d_obs_carry_src.upload(pl.src_ob)); HIPCK(p, dadd.upload(pl.add_ob));
+        HIPCK(p, p->d_po_uv_c.alloc(std::max<size_t>(2 * (size_t)w1.Ep, 1), false)); HIPCK(p, p->d_lo_l_c.alloc(std::max<size_t>(3 * (size_t)w1.El, 1), false)); HIPCK(p, p->d_ob_w_c.alloc(std::max<size_t>((size_t)E1, 1), false));
         const size_t o_wp = 2 * (size_t)s->Ep_add, o_l = o_wp + s->Ep_add, o_wl = o_l + 3 * (size_t)s->El_add;
-        if (E1) hipLaunchKernelGGL(k_obs_carry_gather, dim3((E1 + 255) / 256), dim3(256), 0, p->stream, p->d_po_uv.p, p->d_lo_l.p, p->d_ob_w.p, Ep0, dadd.p, dadd.p + o_wp, dadd.p + o_l, dadd.p + o_wl,
-                                   p->d_obs_carry_src.p, Ep1, El1, p->d_po_uv_c.p, p->d_lo_l_c.p, p->d_ob_w_c.p);
+        if (E1) hipLaunchKernelGGL(k_obs_carry_gather, dim3((E1 + 255) / 256), dim3(256), 0, p->stream, p->d_po_uv.p, p->d_lo_l.p, p->d_ob_w.p, w0.Ep, dadd.p, dadd.p + o_wp, dadd.p + o_l, dadd.p + o_wl,
+                                   p->d_obs_carry_src.p, w1.Ep, w1.El, p->d_po_uv_c.p, p->d_lo_l_c.p, p->d_ob_w_c.p);
         HIPCK(p, hipGetLastError());
         if (!own_stage) HIPCK(p, plba_stream_wait(p, p->stream));      // (shared staging area: every queued copy must have left it before prepare() writes it again)
-        p->carry_po = true; p->carry_lo = true; p->carry_obs_pending = true;
-        p->po_uv.resize(2 * (size_t)Ep1); p->po_w.resize(Ep1); p->lo_l.resize(3 * (size_t)El1); p->lo_w.resize(El1);      // (stale: carry_po / carry_lo)
     }
-    p->po_pt.swap(npo.lm); p->po_kf.swap(npo.kf);
-    p->lo_ln.swap(nlo.lm); p->lo_kf.swap(nlo.kf);
-    p->Ep = (int)p->po_pt.size(); p->El = (int)p->lo_ln.size();
-    // fixed flags and the (stale for kept entries: carry_*) estimate arrays follow the new numbering
-    {
-        std::vector<uint8_t> pf(Np1, 0), lf(Nl1, 0);
-        for (int i = 0; i < Np0; ++i) if (pmap[i] >= 0) pf[pmap[i]] = p->pt_fixed[i];
-        for (int i = 0; i < s->Np_add; ++i) pf[Npk + i] = s->point_fixed ? s->point_fixed[i] : 0;
-        for (int i = 0; i < Nl0; ++i) if (lmap[i] >= 0) lf[lmap[i]] = p->ln_fixed[i];
-        for (int i = 0; i < s->Nl_add; ++i) lf[Nlk + i] = s->line_fixed ? s->line_fixed[i] : 0;
-        p->pt_fixed.swap(pf); p->ln_fixed.swap(lf);
-        p->pts.assign((size_t)Np1 * 3, 0.0); p->lns.assign((size_t)Nl1 * 6, 0.0);
-    }
-    // ---- IMU edges: those of the kept keyframes, shifted, then the added ones -------------------------------------------------------------------
-    {
-        std::vector<int32_t> ni, nj; std::vector<double> npre, nip, nib;
-        for (int m = 0; m < M0; ++m) {
-            if (p->imu_i[m] < nd || p->imu_j[m] < nd) continue;
-            ni.push_back(p->imu_i[m] - nd); nj.push_back(p->imu_j[m] - nd);
-            npre.insert(npre.end(), &p->imu_pre[(size_t)m * 142], &p->imu_pre[(size_t)m * 142] + 142);
-            nip.insert(nip.end(), &p->imu_ipvr[(size_t)m * 81], &p->imu_ipvr[(size_t)m * 81] + 81);
-            nib.insert(nib.end(), &p->imu_ibias[(size_t)m * 36], &p->imu_ibias[(size_t)m * 36] + 36);
-        }
-        for (int m = 0; m < s->M_add; ++m) {
-            ni.push_back(s->imu_kf_i[m]); nj.push_back(s->imu_kf_j[m]);
-            npre.insert(npre.end(), s->preint142 + (size_t)m * 142, s->preint142 + (size_t)m * 142 + 142);
-            nip.insert(nip.end(), s->info_pvr81 + (size_t)m * 81, s->info_pvr81 + (size_t)m * 81 + 81);
-            nib.insert(nib.end(), s->info_bias36 + (size_t)m * 36, s->info_bias36 + (size_t)m * 36 + 36);
-        }
-        p->imu_i.swap(ni); p->imu_j.swap(nj); p->imu_pre.swap(npre); p->imu_ipvr.swap(nip); p->imu_ibias.swap(nib);
-        p->M = (int)p->imu_i.size();
-    }
-    slap("observation carry, imu");
-    p->K = K1; p->Np = Np1; p->Nl = Nl1;
-    p->level.assign((size_t)p->Ep + p->El, 0);      // a new graph: every edge at level 0
+    slap("observation carry");
+    // ---- commit: nothing below can fail -----------------------------------------------------------------------------------------------------
+    std::swap(p->win, p->win_next);
+    p->carry_obs_pending = true;
     p->dirty = true;
-    if (point_map) memcpy(point_map, pmap.data(), (size_t)Np0 * 4);
-    if (line_map) memcpy(line_map, lmap.data(), (size_t)Nl0 * 4);
+    if (point_map) memcpy(point_map, pl.pmap.data(), pl.pmap.size() * 4);
+    if (line_map) memcpy(line_map, pl.lmap.data(), pl.lmap.size() * 4);
     return PLBA_OK;
 }
 
@@ -2869,7 +2707,7 @@ int plba_marginalize_factors(plba_problem* p, int n_imu, const int32_t* imu_edge
 int plba_marginalize_to_prior(plba_problem* p, int first_kf, int max_edges, int32_t* out3) {
     if (!p) return PLBA_ERR_INVALID;
     if (p->world > 1) FAIL(p, PLBA_ERR_STATE, "plba_marginalize_to_prior: a sharded problem is not marginalized on the device");
-    if (first_kf < 0 || first_kf >= p->K) FAIL(p, PLBA_ERR_INVALID, "marginalize: first_kf out of range");      // (before prepare(): window and prior untouched)
+    if (first_kf < 0 || first_kf >= p->win.K) FAIL(p, PLBA_ERR_INVALID, "marginalize: first_kf out of range");      // (before prepare(): window and prior untouched)
     int rc = prepare(p, true);      // (resolves the previous one: its result is this call's old prior)
     if (rc) return rc;
     HIPCK(p, hipSetDevice(p->device));
@@ -2881,16 +2719,16 @@ int plba_compute_marginals(plba_problem* p, plba_marginals* m) {
     if (!p) return PLBA_ERR_INVALID;
     if (!m) FAIL(p, PLBA_ERR_INVALID, "plba_compute_marginals: no plba_marginals");
     if (p->world > 1) FAIL(p, PLBA_ERR_STATE, "plba_compute_marginals: a sharded problem has no marginals on the device");
-    if (!p->have_cam || !p->K) FAIL(p, PLBA_ERR_STATE, "plba_compute_marginals: nothing uploaded");
+    if (!p->win.have_cam || !p->win.K) FAIL(p, PLBA_ERR_STATE, "plba_compute_marginals: nothing uploaded");
     const bool want_pair = (m->want & 2) && m->n_pairs > 0;
     if ((m->want & 2) && m->n_pairs < 0) FAIL(p, PLBA_ERR_INVALID, "plba_compute_marginals: n_pairs < 0");
     if (want_pair && (!m->pairs || !m->pair_cov)) FAIL(p, PLBA_ERR_INVALID, "plba_compute_marginals: pairs / pair_cov missing");
     if (want_pair)
         for (int q = 0; q < 2 * m->n_pairs; ++q)
-            if (m->pairs[q] < 0 || m->pairs[q] >= p->K) FAIL(p, PLBA_ERR_INVALID, "plba_compute_marginals: pair %d names keyframe slot %d of %d", q / 2, m->pairs[q], p->K);
+            if (m->pairs[q] < 0 || m->pairs[q] >= p->win.K) FAIL(p, PLBA_ERR_INVALID, "plba_compute_marginals: pair %d names keyframe slot %d of %d", q / 2, m->pairs[q], p->win.K);
     if ((m->want & 1) && !m->kf_cov) FAIL(p, PLBA_ERR_INVALID, "plba_compute_marginals: kf_cov missing");
-    if ((m->want & 4) && p->Np && !m->pt_cov) FAIL(p, PLBA_ERR_INVALID, "plba_compute_marginals: pt_cov missing");
-    if ((m->want & 8) && p->Nl && !m->ln_cov) FAIL(p, PLBA_ERR_INVALID, "plba_compute_marginals: ln_cov missing");
+    if ((m->want & 4) && p->win.Np && !m->pt_cov) FAIL(p, PLBA_ERR_INVALID, "plba_compute_marginals: pt_cov missing");
+    if ((m->want & 8) && p->win.Nl && !m->ln_cov) FAIL(p, PLBA_ERR_INVALID, "plba_compute_marginals: ln_cov missing");
     int rc = prepare(p, true);      // (slid window, pending prior: as plba_optimize would see them)
     if (rc) return rc;
     HIPCK(p, hipSetDevice(p->device));
@@ -3010,16 +2848,16 @@ int plba_debug_get(plba_problem* p, const char* what, double* out, size_t cap, s
         HIPCK(p, fetch(d.x, ld, hx)); HIPCK(p, fetch(d.xl, (size_t)p->L * 6, hl));
         if (p->L) HIPCK(p, plba_d2h(p, act.data(), d.lm_active, p->L));
         v.assign(hx.begin(), hx.begin() + P);
-        for (int s = 0; s < p->L; ++s) if (act[s]) for (int t = 0; t < (s < p->Np ? 3 : 6); ++t) v.push_back(hl[(size_t)s * 6 + t]);
+        for (int s = 0; s < p->L; ++s) if (act[s]) for (int t = 0; t < (s < p->win.Np ? 3 : 6); ++t) v.push_back(hl[(size_t)s * 6 + t]);
     } else if (w == "hll_pt" || w == "hll_ln") {
         std::vector<double> h; HIPCK(p, fetch(d.hll, (size_t)p->L * 12, h));
         if (w == "hll_pt") {
-            v.resize((size_t)p->Np * 9);
-            for (int i = 0; i < p->Np; ++i) { const double* u = &h[(size_t)i * 12]; double* o = &v[(size_t)i * 9];
+            v.resize((size_t)p->win.Np * 9);
+            for (int i = 0; i < p->win.Np; ++i) { const double* u = &h[(size_t)i * 12]; double* o = &v[(size_t)i * 9];
                 o[0] = u[0]; o[1] = u[1]; o[2] = u[2]; o[3] = u[1]; o[4] = u[3]; o[5] = u[4]; o[6] = u[2]; o[7] = u[4]; o[8] = u[5]; }
         } else {
-            v.assign((size_t)p->Nl * 36, 0.0);
-            for (int i = 0; i < p->Nl; ++i) { const double* u = &h[(size_t)(p->Np + i) * 12]; double* o = &v[(size_t)i * 36];
+            v.assign((size_t)p->win.Nl * 36, 0.0);
+            for (int i = 0; i < p->win.Nl; ++i) { const double* u = &h[(size_t)(p->win.Np + i) * 12]; double* o = &v[(size_t)i * 36];
                 for (int b = 0; b < 2; ++b) { const double* q = u + 6 * b; const int z = b * 3;
                     o[(z + 0) * 6 + z + 0] = q[0]; o[(z + 0) * 6 + z + 1] = q[1]; o[(z + 0) * 6 + z + 2] = q[2];
                     o[(z + 1) * 6 + z + 0] = q[1]; o[(z + 1) * 6 + z + 1] = q[3]; o[(z + 1) * 6 + z + 2] = q[4];
@@ -3027,26 +2865,26 @@ int plba_debug_get(plba_problem* p, const char* what, double* out, size_t cap, s
         }
     } else if (w == "bl_pt" || w == "bl_ln") {
         std::vector<double> h; HIPCK(p, fetch(d.bl, (size_t)p->L * 6, h));
-        if (w == "bl_pt") { v.resize((size_t)p->Np * 3); for (int i = 0; i < p->Np; ++i) memcpy(&v[(size_t)i * 3], &h[(size_t)i * 6], 24); }
-        else { v.resize((size_t)p->Nl * 6); for (int i = 0; i < p->Nl; ++i) memcpy(&v[(size_t)i * 6], &h[(size_t)(p->Np + i) * 6], 48); }
+        if (w == "bl_pt") { v.resize((size_t)p->win.Np * 3); for (int i = 0; i < p->win.Np; ++i) memcpy(&v[(size_t)i * 3], &h[(size_t)i * 6], 24); }
+        else { v.resize((size_t)p->win.Nl * 6); for (int i = 0; i < p->win.Nl; ++i) memcpy(&v[(size_t)i * 6], &h[(size_t)(p->win.Np + i) * 6], 48); }
     } else if (w == "err_pvr" || w == "err_bias") {
-        std::vector<double> h; HIPCK(p, fetch(d.imu_err, (size_t)p->M * 16, h));
+        std::vector<double> h; HIPCK(p, fetch(d.imu_err, (size_t)p->win.M * 16, h));
         const int o = w == "err_pvr" ? 0 : 9, nn = w == "err_pvr" ? 9 : 6;
-        v.resize((size_t)p->M * nn);
-        for (int m = 0; m < p->M; ++m) memcpy(&v[(size_t)m * nn], &h[(size_t)m * 16 + o], nn * 8);
+        v.resize((size_t)p->win.M * nn);
+        for (int m = 0; m < p->win.M; ++m) memcpy(&v[(size_t)m * nn], &h[(size_t)m * 16 + o], nn * 8);
     } else if (w == "err_prior") { HIPCK(p, fetch(d.pr_err, p->pr_nv ? p->pr_n : 0, v)); }
     else if ((w == "err_pt" || w == "err_ln") && p->lm_ok) {      // the fused passes keep no record table: residuals left by the first-iteration pass of debug_build
         std::vector<double> h; HIPCK(p, fetch(p->d_ob_err.p, 2 * (size_t)p->E, h));
-        if (w == "err_pt") v.assign(h.begin(), h.begin() + 2 * (size_t)p->Ep);
-        else { v.assign((size_t)p->El * 3, 0.0); for (int e = 0; e < p->El; ++e) { v[3 * (size_t)e] = h[2 * (size_t)(p->Ep + e)]; v[3 * (size_t)e + 1] = h[2 * (size_t)(p->Ep + e) + 1]; } }
+        if (w == "err_pt") v.assign(h.begin(), h.begin() + 2 * (size_t)p->win.Ep);
+        else { v.assign((size_t)p->win.El * 3, 0.0); for (int e = 0; e < p->win.El; ++e) { v[3 * (size_t)e] = h[2 * (size_t)(p->win.Ep + e)]; v[3 * (size_t)e + 1] = h[2 * (size_t)(p->win.Ep + e) + 1]; } }
     }
     else if (w == "err_pt" || w == "err_ln") {
-        std::vector<double> h; HIPCK(p, fetch(d.erec, ((size_t)p->Ep + 2 * (size_t)p->El) * EREC_UNIT, h));
-        if (w == "err_pt") { v.resize((size_t)p->Ep * 2); for (int e = 0; e < p->Ep; ++e) { const size_t o = (size_t)p->ob_pos[e] * EREC_UNIT; v[2 * (size_t)e] = h[o + EREC_PT_E0]; v[2 * (size_t)e + 1] = h[o + EREC_PT_E0 + 1]; } }      // 64-byte point record
-        else { v.assign((size_t)p->El * 3, 0.0); for (int e = 0; e < p->El; ++e) { const size_t o = (size_t)p->ob_pos[p->Ep + e] * EREC_UNIT; v[3 * (size_t)e] = h[o + 13]; v[3 * (size_t)e + 1] = h[o + 14]; } }
+        std::vector<double> h; HIPCK(p, fetch(d.erec, ((size_t)p->win.Ep + 2 * (size_t)p->win.El) * EREC_UNIT, h));
+        if (w == "err_pt") { v.resize((size_t)p->win.Ep * 2); for (int e = 0; e < p->win.Ep; ++e) { const size_t o = (size_t)p->ob_pos[e] * EREC_UNIT; v[2 * (size_t)e] = h[o + EREC_PT_E0]; v[2 * (size_t)e + 1] = h[o + EREC_PT_E0 + 1]; } }      // 64-byte point record
+        else { v.assign((size_t)p->win.El * 3, 0.0); for (int e = 0; e < p->win.El; ++e) { const size_t o = (size_t)p->ob_pos[p->win.Ep + e] * EREC_UNIT; v[3 * (size_t)e] = h[o + 13]; v[3 * (size_t)e + 1] = h[o + 14]; } }
     } else if (w == "erec") {
         if (p->lm_ok) FAIL(p, PLBA_ERR_STATE, "\"erec\": the fused landmark passes keep no record table");
-        HIPCK(p, fetch(d.erec, ((size_t)p->Ep + 2 * (size_t)p->El) * EREC_UNIT, v));
+        HIPCK(p, fetch(d.erec, ((size_t)p->win.Ep + 2 * (size_t)p->win.El) * EREC_UNIT, v));
     }
     else if (w == "stamps") { HIPCK(p, fetch(d.maxd_part, 80, v)); }
     else if (w == "dbgbuf") { HIPCK(p, fetch(d.dbgbuf, 128, v)); }

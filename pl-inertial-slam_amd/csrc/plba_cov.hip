@@ -334,7 +334,7 @@ __global__ void k_cov_gather(DevBuf d, const double* __restrict__ Sig, int Pp, c
 int cov_run(plba_problem* p, plba_marginals* m) {
     const DevBuf& d = p->dv;
     hipStream_t s = p->stream;
-    const int K = p->K, Np = p->Np, Nl = p->Nl, L = p->L, E = p->E, P = p->P;
+    const int K = p->win.K, Np = p->win.Np, Nl = p->win.Nl, L = p->L, E = p->E, P = p->P;
     const bool want_kf = m->want & 1, want_pair = (m->want & 2) && m->n_pairs > 0, want_pt = m->want & 4, want_ln = m->want & 8;
     const int npairs = want_pair ? m->n_pairs : 0;
     const int Pp = std::max(TILE, (P + TILE - 1) / TILE * TILE), T = Pp / CB;      // (the dense factorisation's padding; ld = Pp)
@@ -346,9 +346,9 @@ int cov_run(plba_problem* p, plba_marginals* m) {
         const bool pt = l < Np;
         const int lm = pt ? l : l - Np;
         for (; e < E; ++e) {
-            const bool ept = e < p->Ep;
-            if (ept != pt || (ept ? p->po_pt[e] : p->lo_ln[e - p->Ep]) != lm) break;
-            const int o = p->off_pvr[ept ? p->po_kf[e] : p->lo_kf[e - p->Ep]];
+            const bool ept = e < p->win.Ep;
+            if (ept != pt || (ept ? p->win.po_pt[e] : p->win.lo_ln[e - p->win.Ep]) != lm) break;
+            const int o = p->off_pvr[ept ? p->win.po_kf[e] : p->win.lo_kf[e - p->win.Ep]];
             if (o >= 0) ob.push_back({e, o});
         }
         const bool fixed = p->lm_fixed[l] != 0;
@@ -372,7 +372,7 @@ int cov_run(plba_problem* p, plba_marginals* m) {
     DArr<Ctrl> ctrl;
     DArr<int32_t> dblk, dent, dpairs, stat, fail, flags, cflags;
     PLBA_HIPCK(p, Hp.alloc((size_t)p->Ppad * p->ld, false)); PLBA_HIPCK(p, bp.alloc(p->ld, false));
-    PLBA_HIPCK(p, ierr.alloc((size_t)std::max(p->M, 1) * 16, false)); PLBA_HIPCK(p, ichi.alloc((size_t)std::max(p->M, 1) * 4, false));
+    PLBA_HIPCK(p, ierr.alloc((size_t)std::max(p->win.M, 1) * 16, false)); PLBA_HIPCK(p, ichi.alloc((size_t)std::max(p->win.M, 1) * 4, false));
     PLBA_HIPCK(p, perr.alloc(std::max(p->pr_n, 1), false)); PLBA_HIPCK(p, pdx.alloc(std::max(p->pr_n, 1), false));
     PLBA_HIPCK(p, pchi.alloc(4, false)); PLBA_HIPCK(p, bpr.alloc(p->ld, false));
     // the dense factorisation's buffers, as plba_dense_solve sizes them, the explicit inverse at full size whatever path the problem's own

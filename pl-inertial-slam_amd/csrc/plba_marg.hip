@@ -1529,33 +1529,33 @@ int marginalize_factors_device(plba_problem* p, const std::vector<int>& imu_edge
     int R = 0;
     std::vector<int> imu_rows;
     for (int m : imu_edges) {
-        if (m < 0 || m >= p->M) PLBA_FAIL(p, PLBA_ERR_INVALID, "marginalize: imu edge %d out of range", m);
-        const int ki = p->imu_i[m], kj = p->imu_j[m];
-        touch(p->vid_pvr[ki], 9, dropped(p->vid_pvr[ki]), ki, 0); touch(p->vid_pvr[kj], 9, dropped(p->vid_pvr[kj]), kj, 0);
-        touch(p->vid_bias[ki], 6, dropped(p->vid_bias[ki]), ki, 1); touch(p->vid_bias[kj], 6, dropped(p->vid_bias[kj]), kj, 1);
+        if (m < 0 || m >= p->win.M) PLBA_FAIL(p, PLBA_ERR_INVALID, "marginalize: imu edge %d out of range", m);
+        const int ki = p->win.imu_i[m], kj = p->win.imu_j[m];
+        touch(p->win.vid_pvr[ki], 9, dropped(p->win.vid_pvr[ki]), ki, 0); touch(p->win.vid_pvr[kj], 9, dropped(p->win.vid_pvr[kj]), kj, 0);
+        touch(p->win.vid_bias[ki], 6, dropped(p->win.vid_bias[ki]), ki, 1); touch(p->win.vid_bias[kj], 6, dropped(p->win.vid_bias[kj]), kj, 1);
         imu_rows.push_back(R); R += 15;
     }
     std::vector<MargObs> obs;
     for (int e : pt_edges) {
-        if (e < 0 || e >= p->Ep) PLBA_FAIL(p, PLBA_ERR_INVALID, "marginalize: point edge %d out of range", e);
-        const int l = p->po_pt[e], k = p->po_kf[e];
+        if (e < 0 || e >= p->win.Ep) PLBA_FAIL(p, PLBA_ERR_INVALID, "marginalize: point edge %d out of range", e);
+        const int l = p->win.po_pt[e], k = p->win.po_kf[e];
         touch(PID_PT(l), 3, true, -1, 0);
-        touch(p->vid_pvr[k], 9, dropped(p->vid_pvr[k]), k, 0);
-        obs.push_back(MargObs{e, R, PID_PT(l), p->vid_pvr[k]});
+        touch(p->win.vid_pvr[k], 9, dropped(p->win.vid_pvr[k]), k, 0);
+        obs.push_back(MargObs{e, R, PID_PT(l), p->win.vid_pvr[k]});
         R += 2;
     }
     for (int e : ln_edges) {
-        if (e < 0 || e >= p->El) PLBA_FAIL(p, PLBA_ERR_INVALID, "marginalize: line edge %d out of range", e);
-        const int l = p->lo_ln[e], k = p->lo_kf[e];
+        if (e < 0 || e >= p->win.El) PLBA_FAIL(p, PLBA_ERR_INVALID, "marginalize: line edge %d out of range", e);
+        const int l = p->win.lo_ln[e], k = p->win.lo_kf[e];
         touch(PID_LN(l), 6, true, -1, 0);
-        touch(p->vid_pvr[k], 9, dropped(p->vid_pvr[k]), k, 0);
-        obs.push_back(MargObs{p->Ep + e, R, PID_LN(l), p->vid_pvr[k]});
+        touch(p->win.vid_pvr[k], 9, dropped(p->win.vid_pvr[k]), k, 0);
+        obs.push_back(MargObs{p->win.Ep + e, R, PID_LN(l), p->win.vid_pvr[k]});
         R += 2;
     }
     int prior_row = -1;
     if (use_prior && p->pr_nv > 0) {
         std::map<int, std::pair<int, int>> by_vid;
-        for (int k = 0; k < p->K; ++k) { by_vid[p->vid_pvr[k]] = {k, 0}; if (p->vid_bias[k] >= 0) by_vid[p->vid_bias[k]] = {k, 1}; }
+        for (int k = 0; k < p->win.K; ++k) { by_vid[p->win.vid_pvr[k]] = {k, 0}; if (p->win.vid_bias[k] >= 0) by_vid[p->win.vid_bias[k]] = {k, 1}; }
         for (int i = 0; i < p->pr_nv; ++i) {
             const auto& kv = by_vid[p->pr_vid[i]];
             touch(p->pr_vid[i], p->pr_size[i], dropped(p->pr_vid[i]), kv.first, kv.second);
@@ -1610,8 +1610,8 @@ int marginalize_factors_device(plba_problem* p, const std::vector<int>& imu_edge
     std::vector<int> imu_desc, vcol, elimL, elimP;
     std::vector<uint8_t> restL(pos, 1), restP;
     for (size_t t = 0; t < imu_edges.size(); ++t) {
-        const int mI = imu_edges[t], ki = p->imu_i[mI], kj = p->imu_j[mI];
-        for (int v : {mI, imu_rows[t], col[p->vid_pvr[ki]], col[p->vid_pvr[kj]], col[p->vid_bias[ki]], col[p->vid_bias[kj]]}) imu_desc.push_back(v);
+        const int mI = imu_edges[t], ki = p->win.imu_i[mI], kj = p->win.imu_j[mI];
+        for (int v : {mI, imu_rows[t], col[p->win.vid_pvr[ki]], col[p->win.vid_pvr[kj]], col[p->win.vid_bias[ki]], col[p->win.vid_bias[kj]]}) imu_desc.push_back(v);
     }
     if (prior_row >= 0) { vcol.resize(p->pr_nv); for (int i = 0; i < p->pr_nv; ++i) vcol[i] = col[p->pr_vid[i]]; }
     for (size_t bq = 0; bq < blk_off.size(); ++bq) for (int t = 0; t < blk_size[bq]; ++t) { elimL.push_back(blk_off[bq] + t); restL[blk_off[bq] + t] = 0; }
@@ -1724,7 +1724,7 @@ int marginalize_factors_device(plba_problem* p, const std::vector<int>& imu_edge
         return drop_on_error.ok();
     }
     // ---- results: two asynchronous copies into pinned memory (the staging area's free tail), ONE synchronisation -------------
-    const size_t nkf = (size_t)p->K * KF_STRIDE;
+    const size_t nkf = (size_t)p->win.K * KF_STRIDE;
     std::vector<double> pageable;
     double* hres = nullptr;
     {
@@ -1804,10 +1804,10 @@ void marg_discard(plba_problem* p) {
 // Factor selection of the call site (src/mapHandler.cpp:6075-6188): first IMU edge, <= NUM+1 point edges and
 // <= NUM+1 line edges whose landmark was first observed in the oldest keyframe, the old prior; drop that keyframe.
 int marginalize_device(plba_problem* p, int first_kf, int max_edges, plba_prior* out) {
-    if (first_kf < 0 || first_kf >= p->K) PLBA_FAIL(p, PLBA_ERR_INVALID, "marginalize: first_kf out of range");
+    if (first_kf < 0 || first_kf >= p->win.K) PLBA_FAIL(p, PLBA_ERR_INVALID, "marginalize: first_kf out of range");
     const int NUM = max_edges;
     std::vector<int> imu, pts, lns, drop;
-    if (p->M > 0) imu.push_back(0);
+    if (p->win.M > 0) imu.push_back(0);
     auto select = [&](const std::vector<int32_t>& lm_of, const std::vector<int32_t>& kf_of, int E, int N, std::vector<int>& outv) {
         int num = 0, e = 0;
         for (int l = 0; l < N && num <= NUM; ++l) {
@@ -1817,10 +1817,10 @@ int marginalize_device(plba_problem* p, int first_kf, int max_edges, plba_prior*
             for (int a = e0; a < e; ++a) { outv.push_back(a); if (++num > NUM) break; }   // `num>NUM` admits NUM+1 (B-Q10)
         }
     };
-    select(p->po_pt, p->po_kf, p->Ep, p->Np, pts);
-    select(p->lo_ln, p->lo_kf, p->El, p->Nl, lns);
-    drop.push_back(p->vid_pvr[first_kf]);
-    if (p->vid_bias[first_kf] >= 0) drop.push_back(p->vid_bias[first_kf]);
+    select(p->win.po_pt, p->win.po_kf, p->win.Ep, p->win.Np, pts);
+    select(p->win.lo_ln, p->win.lo_kf, p->win.El, p->win.Nl, lns);
+    drop.push_back(p->win.vid_pvr[first_kf]);
+    if (p->win.vid_bias[first_kf] >= 0) drop.push_back(p->win.vid_bias[first_kf]);
     return marginalize_factors_device(p, imu, pts, lns, true, drop, out);
 }
 

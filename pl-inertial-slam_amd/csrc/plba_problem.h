@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "plba_internal.h"
+#include "plba_window.h"
 
 namespace plba {
 
@@ -277,22 +278,11 @@ struct plba_problem {
     plba::DevBatch sbatch;
     plba::DArr<double> d_wtw;          // W^T W tiles of the chain Schur complement (fused landmark path, one GPU: formed in the gather launch)
     plba::DArr<double> d_twin_alt;     // ... and so are its landmark blocks and the pose-side assembly     // the next iteration's linearisation is already in the stream (enqueued behind k_decide)
-    // ---- host copy of the uploaded graph -------------------------------------------------------
-    bool have_cam = false;
-    double fx, fy, cx, cy, Rbc[9], Pbc[3], gw[3] = {0, 0, 0};
-    int K = 0, Np = 0, Nl = 0, Ep = 0, El = 0, M = 0;
-    std::vector<int32_t> vid_pvr, vid_bias;
-    std::vector<double> kf0;              // K x 24 initial records
-    std::vector<uint8_t> fix_pvr, fix_bias;
-    std::vector<double> lm0;              // L x 6
-    std::vector<uint8_t> lm_fixed;        // L
-    std::vector<double> pts, lns;
-    std::vector<uint8_t> pt_fixed, ln_fixed;
-    std::vector<int32_t> po_pt, po_kf, lo_ln, lo_kf;
-    std::vector<double> po_uv, po_w, lo_l, lo_w;
-    std::vector<uint8_t> level;           // E (points then lines)
-    std::vector<int32_t> imu_i, imu_j;
-    std::vector<double> imu_pre, imu_ipvr, imu_ibias;
+    // ---- host copy of the uploaded graph: one value (plba_window.h) -------------------------------------
+    // `win` is what the plba_set_* entry points wrote and prepare() builds the device image from; plba_slide_window plans the next window
+    // into `win_next` (with `slide`: what only its device stage needs) and swaps the two at its commit point.  Both keep their capacity.
+    plba::Window win, win_next;
+    plba::SlidePlan slide;
     int pr_n = 0, pr_nv = 0;
     std::vector<int32_t> pr_vid, pr_size, pr_idx;
     std::vector<double> pr_x0, pr_J0, pr_r0;
@@ -316,23 +306,23 @@ struct plba_problem {
     bool dirty = true;                    // device image must be rebuilt
     int P = 0, Ppad = 0, ld = 0, L = 0, E = 0;
     std::vector<int32_t> off_pvr, off_bias;
+    std::vector<double> lm0;              // L x 6: points and lines in unified slots (prepare(); not formed for a slid window)
+    std::vector<uint8_t> lm_fixed;        // L
     int cur = 0;                          // index of the current estimate buffers
     // ---- device ----------------------------------------------------------------------------------
     plba::DArr<double> d_kf[2], d_kf_saved, d_lm[2], d_lm_saved;
     // plba_slide_window: the kept landmarks' estimates never leave the device.  d_lm_carry holds the NEW window's landmark array (kept ones
     // gathered from the previous window's current estimates, added ones uploaded); prepare() copies it on the device instead of uploading
-    // `pts` / `lns`, whose entries for the kept landmarks are stale while carry_pts / carry_lns are set (plba_set_points / _lines clear them)
-    plba::DArr<double> d_lm_carry, d_kf_carry;      // (and the kept keyframes' states: kf0 is stale while carry_kf is set; plba_set_keyframes clears it)
+    // `pts` / `lns`, whose entries for the kept landmarks are stale while win.carry_pts / carry_lns are set (plba_set_points / _lines clear them)
+    plba::DArr<double> d_lm_carry, d_kf_carry;      // (and the kept keyframes' states: kf0 is stale while win.carry_kf is set; plba_set_keyframes clears it)
     plba::DArr<int32_t> d_lm_carry_src;
-    bool carry_pts = false, carry_lns = false, carry_kf = false;
     // ... and neither do the kept observations' measurements and weights: the slide gathers the new landmark-major arrays on the device
     // (into the *_c buffers: `carry_obs_pending`, swapped in by prepare()); po_uv / po_w / lo_l / lo_w on the host are then stale
-    // (carry_po / carry_lo; plba_set_point_obs / plba_set_line_obs clear them)
+    // (win.carry_po / carry_lo; plba_set_point_obs / plba_set_line_obs clear them)
     plba::DArr<double> d_po_uv_c, d_lo_l_c, d_ob_w_c;
     plba::DArr<double> d_slide_kf, d_slide_lm, d_slide_ob;      // the slide's uploaded additions (members: the gathers that read them are only QUEUED when the slide returns)
     plba::DArr<int32_t> d_obs_carry_src;
-    bool carry_po = false, carry_lo = false, carry_obs_pending = false;
-    std::vector<int32_t> scr_lm[2], scr_kf[2], scr_src[2];      // the slide's merged lists are built here and swapped with po_pt / po_kf / lo_ln / lo_kf: no fresh pages per slide
+    bool carry_obs_pending = false;      // the d_*_c buffers hold the next window's arrays: set at the slide's commit, cleared by prepare()
     plba::DArr<double> d_po_uv, d_lo_l, d_ob_w, d_ob_chi2, d_erec, d_erec2;
     plba::DArr<int32_t> d_ob_kf, d_ob_slot, d_lm_start, d_off_pvr, d_off_bias;
     plba::DArr<uint8_t> d_level, d_lm_fixed, d_lm_active, d_depth;

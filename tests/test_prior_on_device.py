@@ -283,6 +283,36 @@ def test_set_prior_after_marginalize_to_prior(pkg, hip):
     _same_results(out[0][1], out[1][1], "set_prior after marginalize_to_prior")
 
 
+def test_refused_set_prior_leaves_a_device_made_prior_as_it_was(pkg, hip):
+    """plba_set_prior validates before it touches anything: a call refused for a bad `size` entry — once while the marginalization
+    that makes the prior is still pending, once after it has been resolved — leaves the device-made prior in place.  plba_get_prior and
+    the next two-stage BA are those of a twin handle that never made the refused calls, bit for bit."""
+    w = pkg.window.make_window(12, 260, 50, imu=True, seed=23)
+    bad = dict(n=15, vid=np.array([0, 1], np.int32), size=np.array([9, 7], np.int32), idx=np.array([0, 9], np.int32),
+               x0=np.zeros(16), J0=np.eye(15), r0=np.zeros(15))
+    out = []
+    for refused in (True, False):
+        p = pkg.new_problem(); p.upload_window(w); pkg.protocol.local_ba(p)
+        p.marginalize_to_prior(0, 50)
+        if refused:
+            with pytest.raises(pkg.abi.PlbaError, match="Undefined size of marginalization vertex: 7"):
+                p.set_prior(bad)
+        first = p.get_prior()
+        if refused:
+            with pytest.raises(pkg.abi.PlbaError, match="Undefined size of marginalization vertex: 7"):
+                p.set_prior(bad)
+        again = p.get_prior()
+        _same_prior(first, again, "read twice")
+        assert first["m"] > 0 and first["Ar"] is not None      # still the device-made one
+        _restore_robust(p, w)
+        r = pkg.protocol.local_ba(p)
+        out.append((first, _stats(r), pkg.protocol.results(p)))
+        p.close()
+    _same_prior(out[0][0], out[1][0], "after the refused set_prior")
+    assert out[0][1] == out[1][1], (out[0][1], out[1][1])
+    _same_results(out[0][2], out[1][2], "BA after the refused set_prior")
+
+
 def test_refusals(pkg, hip):
     w = pkg.window.make_window(8, 150, 40, imu=True, seed=29)
     p = pkg.new_problem(); p.upload_window(w); pkg.protocol.local_ba(p)
