@@ -774,32 +774,6 @@ static void build_lm_groups(const plba_problem* p, const std::vector<int32_t>& l
     glap("gather lists");
 }
 
-// Dependent launches the multi-chain factorisation needs for T tiles of 32 columns and a band of hbt sub-diagonal tiles: the same
-// arithmetic as the plan builder in prepare() (two chains; four chains; four chains with the separator region taken as a second
-// stage), without building anything — used to choose the chain elimination's segment length.
-static int twin_launch_estimate(int T, int hbt) {
-    if (T < 8 || hbt < 1) return T;
-    int best = T - 1;
-    for (int variant = 0; variant < 3; ++variant) {
-        const int nch = variant == 0 ? 2 : 4, nsep = nch - 1;
-        const bool nested = variant == 2;
-        const int nC = (T - nsep * hbt - nch / 2) / nch;
-        if (nC < 1) continue;
-        int left = T - nsep * hbt - nch / 2 - nch * nC;
-        int w[3] = {0, 0, 0};
-        for (int q = 0; q < nsep; ++q) { w[q] = hbt + (left > 0 ? 1 : 0); if (left > 0) --left; }
-        const int stage1 = nC + 1, m0 = nch * nC + nch / 2;
-        int launches;
-        if (nested) {
-            const int lenA = w[0], lenB = std::min(w[2], lenA - 1);
-            if (lenB < 1) continue;
-            launches = stage1 + lenA + (T - (m0 + w[0] + lenB) - 1);
-        } else launches = stage1 + (T - m0 - 1);
-        best = std::min(best, launches);
-    }
-    return best + 1;      // + the launch that ends the factorisation (k_chol32's last step)
-}
-
 // Padded dimension of the compact dense system.  The block steps are 32 columns wide; the 64-column forms (factor_block 64, wide steps, the
 // dataflow factorisation, the 64 x 64 inverses of the substitution-based back-solve for systems beyond 32 steps) need a multiple of 64.  A
 // SMALL system — one that stays below 8 tiles even padded to 64, i.e. the plain multi-launch factorisation with the explicit inverse, never the
@@ -1303,7 +1277,7 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
             // segment length.  Longer segments leave fewer separators dense — fewer tiles for the factorisation — but what counts is the number
             // of DEPENDENT launches of the multi-chain plan, which is not monotonic in it: the band's width in tiles depends on where the
             // segment windows fall on tile boundaries (configs[2]: 4 blocks -> 375 dims, 7 launches; 6 -> 357, 6; 7 -> 348, 7; 8 -> 339, 6).
-            // So every candidate gets its dense layout, its band and the plan builder's launch count (twin_launch_estimate), ~10.3 us per
+            // So every candidate gets its dense layout, its band and the plan builder's launch count (twin_plan_launches, plba_twin_plan.h), ~10.3 us per
             // launch; a chain block costs the trial launch ~2.3 us of back-substitution in front of the IMU edge blocks where that path is
             // the launch's critical one (small windows), nothing where the landmark pass is longer.  tools/ab_env.py, one process, medians,
             // configs[2]: 4 -> 0.1720 ms per trial, 5 -> 0.1744, 6 -> 0.1672, 8 -> 0.1708: the order this cost gives.
@@ -1330,7 +1304,7 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
                 for (int q = 0; q + 1 < npos; ++q) span(q, q + 1);      // IMU edges between neighbours
                 { int lo = npos, hi = -1; for (int q = 0; q < npos; ++q) if (forced[q]) { lo = std::min(lo, q); hi = std::max(hi, q); } if (hi >= 0) span(lo, hi); }      // the prior's kept vertices
                 const bool twin = p->opt.band_solve == 1 && T <= TWIN_MAX_TILES;
-                const int launches = twin ? twin_launch_estimate(T, hb) : T;
+                const int launches = twin ? twin_plan_launches(T, hb) : T;
                 const double cost = 10.3 * launches + block_cost * seg;
                 if (ptime) fprintf(stderr, "[prepare]   chain segments of %d: %d dense dims, %d tiles, band %d -> %d launches (cost %.1f)\n", seg, pd, T, hb, launches, cost);
                 if (cost < best_cost) { best_cost = cost; best_seg = seg; p->seg_launch_est = launches; }
@@ -1712,193 +1686,23 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
                 p->dd.band = 1;
             } else if (twin_pref && hbt >= 1) {
                 if (!p->dd.Ninv) { HIPCK(p, p->d_Ninvd.alloc((size_t)2 * cv.Pdpad * cv.Pdpad)); p->dd.Ninv = p->d_Ninvd.p; p->dd.Nwork = p->dd.Ninv + (size_t)cv.Pdpad * cv.Pdpad; }
-                // Chains and separators (plba_dense.hip, "Multi-chain factorisation").  Natural layout of the band:
-                //   two chains :  C0 (n + 1 tiles) | S1 | C1 (n tiles, eliminated bottom-up)
-                //   four chains:  C0 (n + 1) | S1 | C1 (n) | S2 | C2 (n + 1) | S3 | C3 (n, bottom-up)
-                // separators >= hbt tiles wide (chains must not couple); C1 / C3 accumulate their separator updates in `alt` and are one tile
-                // shorter, so that the last step of C0 / C2 folds those in.  With four chains the separator region [S1 S2 S3] is itself
-                // block-tridiagonal and is taken the same way once more (second stage): S1 top-down and S3 bottom-up (one tile shorter,
-                // accumulating in `alt2`) towards S2.  The variant with the fewest dependent launches is taken.
-                struct Chain { int nat0, len; bool rev; int alt; int stage; std::vector<int> later, rows; int p0; };      // alt: 0 = writes sys, 1 = alt, 2 = alt2
-                struct Region { int nat0, w; };
-                auto build = [&](int nch, bool nested, std::vector<Chain>& chains, int& launches, int& f0_out, int& m0_out, std::vector<int32_t>& perm) {
-                    chains.clear(); launches = 1 << 30;
-                    const int nsep = nch - 1;
-                    const int nC = (T - nsep * hbt - nch / 2) / nch;      // nch / 2 chains carry the extra tile
-                    if (nC < 1) return;
-                    int left = T - nsep * hbt - nch / 2 - nch * nC;      // tiles that do not divide: widen the first separators
-                    std::vector<Region> seps;
-                    int at = 0;
-                    for (int c = 0; c < nch; ++c) {
-                        Chain ch; ch.nat0 = at; ch.len = nC + ((c & 1) ? 0 : 1); ch.alt = (c & 1) ? 1 : 0; ch.rev = (c == nch - 1); ch.stage = 0; ch.p0 = 0;
-                        at += ch.len;
-                        chains.push_back(ch);
-                        if (c < nsep) { const int w = hbt + (left > 0 ? 1 : 0); if (left > 0) --left; seps.push_back({at, w}); at += w; }
-                    }
-                    // permuted positions: level-1 chains, then (nested) S1 | S3 reversed | S2, else the separators in natural order
-                    int pt = 0;
-                    for (auto& ch : chains) { ch.p0 = pt; pt += ch.len; }
-                    m0_out = pt;
-                    std::vector<int> sep_p0(nsep, 0);
-                    std::vector<char> sep_rev(nsep, 0);
-                    int lenA = 0, lenB = 0;
-                    if (nested && nsep == 3) {
-                        lenA = seps[0].w; lenB = std::min(seps[2].w, lenA - 1);
-                        if (lenB < 1) return;
-                        sep_p0[0] = pt; pt += seps[0].w;
-                        sep_p0[2] = pt; pt += seps[2].w; sep_rev[2] = 1;
-                        sep_p0[1] = pt; pt += seps[1].w;
-                    } else {
-                        if (nested) return;
-                        for (int q = 0; q < nsep; ++q) { sep_p0[q] = pt; pt += seps[q].w; }
-                    }
-                    perm.assign(cv.Pdpad, 0);
-                    auto map_range = [&](int nat0, int w, int p0, bool rev) {
-                        for (int j = 0; j < w; ++j)
-                            for (int e = 0; e < 32; ++e) perm[(nat0 + j) * 32 + e] = rev ? (p0 + (w - 1 - j)) * 32 + (31 - e) : (p0 + j) * 32 + e;
-                    };
-                    for (const auto& ch : chains) map_range(ch.nat0, ch.len, ch.p0, ch.rev);
-                    for (int q = 0; q < nsep; ++q) map_range(seps[q].nat0, seps[q].w, sep_p0[q], sep_rev[q] != 0);
-                    auto tiles_of = [&](int q) { std::vector<int> v; for (int j = 0; j < seps[q].w; ++j) v.push_back(sep_p0[q] + j); return v; };
-                    for (int c = 0; c < nch; ++c) {      // what a level-1 chain couples with beyond itself: its adjacent separators
-                        std::vector<int> qs;
-                        if (c == 0) qs = {0}; else if (c == nch - 1) qs = {nsep - 1}; else qs = {c - 1, c};
-                        for (int q : qs) { auto v = tiles_of(q); chains[c].later.insert(chains[c].later.end(), v.begin(), v.end()); }
-                        std::sort(chains[c].later.begin(), chains[c].later.end());
-                    }
-                    int stage1 = 0;
-                    for (const auto& ch : chains) stage1 = std::max(stage1, ch.len);
-                    if (nested) {
-                        // second stage: S1 (all of it) and the first lenB tiles of the turned-around S3; what is left of S3 joins S2 as the final block
-                        Chain a; a.nat0 = 0; a.len = lenA; a.rev = false; a.alt = 0; a.stage = 1; a.p0 = sep_p0[0];
-                        Chain b2; b2.nat0 = 0; b2.len = lenB; b2.rev = true; b2.alt = 2; b2.stage = 1; b2.p0 = sep_p0[2];
-                        f0_out = sep_p0[2] + lenB;
-                        for (int t2 = f0_out; t2 < T; ++t2) { a.later.push_back(t2); b2.later.push_back(t2); }
-                        for (int c : {0, 1}) for (int j = 0; j < chains[c].len; ++j) a.rows.push_back(chains[c].p0 + j);      // rows with support on S1's columns
-                        for (int c : {2, 3}) for (int j = 0; j < chains[c].len; ++j) b2.rows.push_back(chains[c].p0 + j);
-                        chains.push_back(a); chains.push_back(b2);
-                        launches = stage1 + lenA + (T - f0_out - 1);
-                    } else {
-                        f0_out = m0_out;
-                        launches = stage1 + (T - f0_out - 1);
-                    }
-                };
-                std::vector<Chain> chains, ctry;
-                std::vector<int32_t> perm, ptry;
-                int launches = 1 << 30, f0 = 0, m0 = 0;
-                for (int variant = 0; variant < 3; ++variant) {
-                    int l = 0, f = 0, m = 0;
-                    build(variant == 0 ? 2 : 4, variant == 2, ctry, l, f, m, ptry);
-                    if (l < launches) { launches = l; f0 = f; m0 = m; chains.swap(ctry); perm.swap(ptry); }
-                }
-                if (launches < T - 1) {
-                    TwinView& tv = p->twinv;
-                    const int n32 = cv.Pdpad;
-                    tv.T = T; tv.m0 = f0; tv.nchains = (int)chains.size();
-                    std::vector<int32_t> xmap(n32), fac(T, -1);
-                    for (int i = 0; i < n32; ++i) xmap[perm[i]] = i;
-                    for (const auto& ch : chains) if (ch.stage == 0) fac[ch.rev ? ch.nat0 + ch.len - 1 : ch.nat0] = ch.p0 | (ch.rev ? 1 << 16 : 0);
-                    std::vector<TwinTile> list;
-                    tv.off.assign(1, 0);
-                    int nlaunch = 0;
-                    for (int stage = 0; stage < 2; ++stage) {
-                        int nl = 0;
-                        for (const auto& ch : chains) if (ch.stage == stage) nl = std::max(nl, ch.len);
-                        // the tile a sys-writing chain's last step factors by look-ahead: the first tile of the next stage's first chain (or of
-                        // the final block), and — first stage of a nested plan — C2's last step factors the second-stage chain S3's first tile
-                        for (int t = 0; t < nl; ++t) {
-                            int ci_stage = 0;
-                            for (size_t ci = 0; ci < chains.size(); ++ci) {
-                                const Chain& ch = chains[ci];
-                                if (ch.stage != stage) continue;
-                                const int cis = ci_stage++;
-                                if (t >= ch.len) continue;
-                                const int k = ch.p0 + t;
-                                const bool last = (t == ch.len - 1);
-                                std::vector<int> S;
-                                for (int c = k + 1; c < ch.p0 + ch.len; ++c) S.push_back(c);
-                                S.insert(S.end(), ch.later.begin(), ch.later.end());
-                                std::sort(S.begin(), S.end());
-                                const int later0 = ch.later.empty() ? T : *std::min_element(ch.later.begin(), ch.later.end());
-                                auto in_later = [&](int x) { return std::binary_search(ch.later.begin(), ch.later.end(), x); };
-                                auto push = [&](int r, int c, int aj, int flags) { TwinTile e; e.r = (int16_t)r; e.c = (int16_t)c; e.aj = (int16_t)aj; e.flags = (int16_t)flags; e.k = (int16_t)k; e.pad = 0; list.push_back(e); };
-                                const bool fold = ch.alt == 0 && last;      // this step folds the accumulating chains' part of its later tiles in
-                                const int asel = stage == 1 ? 32 : 0;         // second stage accumulates in alt2
-                                // look-ahead targets of a folding step
-                                int look1 = -1;
-                                if (fold) {
-                                    if (stage == 0) {
-                                        bool has_stage1 = false;
-                                        for (const auto& c2 : chains) has_stage1 |= c2.stage == 1;
-                                        if (cis == 0) look1 = has_stage1 ? chains[chains.size() - 2].p0 : f0;        // C0: S1's first tile (= m0), or the final block's
-                                        else if (has_stage1 && cis == 2) look1 = chains.back().p0;                     // C2: the turned-around S3's first tile
-                                    } else if (cis == 0) look1 = f0;                                                     // S1: the final block's first tile
-                                }
-                                (void)later0;
-                                for (size_t a2 = 0; a2 < S.size(); ++a2)
-                                    for (size_t b2 = 0; b2 <= a2; ++b2) {
-                                        const int r = S[a2], c = S[b2];
-                                        const bool ss = in_later(r) && in_later(c);
-                                        push(r, c, -1, ((ch.alt && ss) ? (1 | asel) : 0) | ((last && r == k + 1) ? 2 : 0) | (c == S[0] ? 4 : 0) | ((fold && ss) ? (8 | asel) : 0) | ((fold && r == look1 && c == look1) ? 16 : 0));
-                                    }
-                                if (fold && stage == 0 && cis == 0)      // separator cross blocks only an accumulating chain writes ((S2, S1) by C1): folded in here, with a zero panel
-                                    for (size_t c2 = 0; c2 < chains.size(); ++c2) {
-                                        const Chain& oc = chains[c2];
-                                        if (oc.stage != 0 || oc.alt == 0 || c2 == 0 || c2 + 1 == chains.size()) continue;
-                                        // oc.later = two separators' tiles: every (r, c) pair with r, c in DIFFERENT separators
-                                        for (int r : oc.later) for (int c : oc.later) {
-                                            if (r <= c) continue;
-                                            bool same = false;      // same separator <=> covered by a sys-writer's own list
-                                            for (size_t c3 = 0; c3 < chains.size(); ++c3) {
-                                                const Chain& sc = chains[c3];
-                                                if (sc.stage != 0 || sc.alt != 0) continue;
-                                                if (std::binary_search(sc.later.begin(), sc.later.end(), r) && std::binary_search(sc.later.begin(), sc.later.end(), c)) same = true;
-                                            }
-                                            if (!same) push(r, c, -1, 8);
-                                        }
-                                    }
-                                for (int c : S) push(T, c, -1, ((ch.alt && in_later(c)) ? (1 | asel) : 0) | (c == S[0] ? 4 : 0) | ((fold && in_later(c)) ? (8 | asel) : 0));
-                                for (int aj : ch.rows) for (int c : S) push(T, c, aj, c == S[0] ? 4 : 0);
-                                for (int aj = ch.p0; aj < k; ++aj) for (int c : S) push(T, c, aj, c == S[0] ? 4 : 0);
-                                {   // the identity row that STARTS at this step is initialised over every later tile of the system, not only the ones this
-                                    // chain couples with: later stages read R(k, c) for all of them, and a block left untouched would hold the previous
-                                    // solve's values
-                                    std::vector<int> Sall;
-                                    for (int c : S) if (c < ch.p0 + ch.len) Sall.push_back(c);
-                                    for (int c = (stage == 0 ? m0 : f0); c < T; ++c) Sall.push_back(c);
-                                    for (int c : Sall) push(T, c, k, c == Sall[0] ? 4 : 0);
-                                }
-                            }
-                            tv.off.push_back((int)list.size());
-                        }
-                        nlaunch += nl;
-                    }
-                    tv.nlaunch = nlaunch;
-                    HIPCK(p, p->d_twin_list.upload(list)); HIPCK(p, p->d_twin_perm.upload(perm)); HIPCK(p, p->d_twin_xmap.upload(xmap)); HIPCK(p, p->d_twin_fac.upload(fac));
-                    {   // k_chain_schur's workgroup order: at 44 tiles the launch is two rounds of workgroups, and a chain's first tile — 6 us of
-                        // factorisation behind its own Schur update — must not start in the second one
-                        std::vector<int32_t> order;
-                        for (int t2 = 0; t2 < T; ++t2) if (fac[t2] >= 0) order.push_back((t2 << 16) | t2);
-                        for (int dist = 0; dist <= T; ++dist) for (int ta = dist; ta < T; ++ta) { const int tb = ta - dist; if (dist == 0 && fac[ta] >= 0) continue; order.push_back((ta << 16) | tb); }
-                        for (int tb = 0; tb < T; ++tb) order.push_back((T << 16) | tb);
-                        HIPCK(p, p->d_cs_order.upload(order)); p->dd.cs_order = p->d_cs_order.p;
-                    }
+                TwinPlan pl;      // (plba_twin_plan.h: chains and separators, the permutation, the tile list of every launch, k_chain_schur's order)
+                if (twin_plan_build(T, hbt, pl)) {
+                    HIPCK(p, p->d_twin_list.upload(pl.list)); HIPCK(p, p->d_twin_perm.upload(pl.perm)); HIPCK(p, p->d_twin_xmap.upload(pl.xmap)); HIPCK(p, p->d_twin_fac.upload(pl.fac));
+                    HIPCK(p, p->d_cs_order.upload(pl.cs_order));
                     HIPCK(p, p->d_twin_alt.alloc((size_t)2 * (cv.Pdpad + TILE) * cv.Pdpad));
-                    tv.list = p->d_twin_list.p;
-                    p->dd.twin_m0 = m0; p->dd.twin_fac = p->d_twin_fac.p; p->dd.perm = p->d_twin_perm.p; p->dd.xmap = p->d_twin_xmap.p;
+                    TwinView& tv = p->twinv;
+                    tv.T = T; tv.final0 = pl.final0; tv.nchains = pl.nchains; tv.nlaunch = pl.nlaunch; tv.list = p->d_twin_list.p; tv.off.swap(pl.off);
+                    p->dd.twin_m0 = pl.sep0; p->dd.twin_fac = p->d_twin_fac.p; p->dd.cs_order = p->d_cs_order.p; p->dd.perm = p->d_twin_perm.p; p->dd.xmap = p->d_twin_xmap.p;
                     p->dd.alt = p->d_twin_alt.p; p->dd.alt2 = p->d_twin_alt.p + (size_t)(cv.Pdpad + TILE) * cv.Pdpad;
                     p->twin_ok = true;
-                    // the plan as chosen, for debug_get "solver_plan": first-stage chains in natural order, the separators between them
-                    std::vector<std::pair<int, int>> nat;
-                    for (const auto& ch : chains) if (ch.stage == 0) nat.push_back({ch.nat0, ch.len});
-                    p->plan_twin[0] = (double)nat.size(); p->plan_twin[1] = chains.size() > nat.size() ? 1.0 : 0.0;
-                    for (size_t q = 0; q + 1 < nat.size() && q < 3; ++q) p->plan_twin[2 + q] = (double)(nat[q + 1].first - nat[q].first - nat[q].second);
+                    std::copy(pl.summary, pl.summary + 5, p->plan_twin);      // the plan as chosen, for debug_get "solver_plan"
                 }
             }
             plan_hbt = hbt;
         }
         if (ptime) fprintf(stderr, "[prepare] dense system: %d dims, %d tiles, band %d sub-diagonal tiles -> %s\n", cv.Pd, T, hbt, p->band_ok ? "banded twisted solve in LDS" : p->twin_ok ? "multi-chain multi-launch factorisation" : "dense path");
-        if (ptime && p->twin_ok) fprintf(stderr, "[prepare] %d chains, %d + %d dependent launches\n", p->twinv.nchains, p->twinv.nlaunch, p->twinv.T - p->twinv.m0 - 1);
+        if (ptime && p->twin_ok) fprintf(stderr, "[prepare] %d chains, %d + %d dependent launches\n", p->twinv.nchains, p->twinv.nlaunch, p->twinv.T - p->twinv.final0 - 1);
     }
     p->plan_hbt = plan_hbt;
     HIPCK(p, darr_flush());
@@ -2905,10 +2709,10 @@ int plba_debug_get(plba_problem* p, const char* what, double* out, size_t cap, s
         v = {(double)(p->band_ok ? 3 : p->twin_ok ? 2 : p->chain_ok ? 1 : 0), (double)((p->chain_ok ? p->cv.Pdpad : p->Ppad) / 32), ninv ? 1.0 : 0.0, (double)p->plan_hbt,
              p->plan_twin[0], p->plan_twin[1], p->plan_twin[2], p->plan_twin[3], p->plan_twin[4], (double)(p->band_ok ? p->bandv.nA : 0), (double)(p->band_ok ? p->bandv.nB : 0)};
     }
-    else if (w == "fact_launches_estimate") v = {(double)p->seg_launch_est};      // what the segment-length choice expected (twin_launch_estimate): fact_launches + 1 when the plan is built
+    else if (w == "fact_launches_estimate") v = {(double)p->seg_launch_est};      // what the segment-length choice expected (twin_plan_launches, plba_twin_plan.h): fact_launches + 1 when the plan is built
     else if (w == "fact_launches") {      // dependent launches of one factorisation between the profile events 11 and 12 (bench.py's roofline)
         if (p->band_ok) v = {2.0};
-        else if (p->twin_ok) v = {(double)(p->twinv.nlaunch + (p->twinv.T - p->twinv.m0 - 1))};
+        else if (p->twin_ok) v = {(double)(p->twinv.nlaunch + (p->twinv.T - p->twinv.final0 - 1))};
         else v = {-1.0};
     }
     else if (w == "chi2") { HIPCK(p, plba_d2h(p, p->h_ctrl, d.ctrl, sizeof(Ctrl))); v = {p->h_ctrl->current_chi}; }

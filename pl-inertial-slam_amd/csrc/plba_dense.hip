@@ -1016,12 +1016,12 @@ static void launch_cholesky_nb(const DevBuf& d, bool use_mfma, hipStream_t s) {
 }
 static bool inverse_panels(const DevBuf& d, bool use_mfma) { return d.fb == 32 && use_mfma; }
 void launch_twin_cholesky(const DevBuf& d, const TwinView& tv, hipStream_t s) {
-    const int T = tv.T, m0 = tv.m0;
+    const int T = tv.T;
     for (int t = 0; t < tv.nlaunch; ++t) {
         const int n = tv.off[t + 1] - tv.off[t];
         if (n > 0) hipLaunchKernelGGL(k_chol32_list, dim3(n), dim3(256), 0, s, d, T, tv.list + tv.off[t]);
     }
-    for (int k = m0; k < T - 1; ++k) {      // the last step (panels only) is folded into k_back_gemv, as in launch_cholesky
+    for (int k = tv.final0; k < T - 1; ++k) {      // the last step (panels only) is folded into k_back_gemv, as in launch_cholesky
         const int nt = T - k - 1;
         const int tiles = nt * (nt + 1) / 2 + nt;
         hipLaunchKernelGGL(k_chol32, dim3((tiles > 0 ? tiles : 1) + (k + 1) * (nt > 0 ? nt : 1)), dim3(256), 0, s, d, k, T);

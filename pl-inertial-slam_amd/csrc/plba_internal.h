@@ -24,6 +24,7 @@
 
 #include "plba.h"
 #include "plba_math.h"
+#include "plba_twin_plan.h"
 
 namespace plba {
 
@@ -128,7 +129,7 @@ struct DevBuf {  // trivially-copyable view of device pointers passed to kernels
     int band;              // 1: the banded twisted solver handles this system (plba_band.hip): k_chain_schur leaves tile (0,0) unfactored
     // multi-chain ("twin") form of the multi-launch factorisation of a banded system (plba_dense.hip): the system is stored
     // PERMUTED [chain 0 | chain 1 | ... | separators], so that the chains are independent stretches of one Cholesky
-    int twin_m0;           // first (permuted) tile of the separator region; 0: off
+    int twin_m0;           // first (permuted) SEPARATOR tile (TwinPlan::sep0, not the final block's first tile); 0: off
     const int32_t* cs_order;   // k_chain_schur: tile (ta << 16 | tb) of each workgroup — the tiles that are factored on the spot first, then the band, then the rest; null = natural order
     const int32_t* twin_fac;   // per NATURAL diagonal tile: -1, or the permuted tile it becomes as the first tile of a chain (| 1 << 16: turned
                                // around) — k_chain_schur factors those on the spot
@@ -279,14 +280,10 @@ size_t band_lds_bytes(int Pdpad);
 void launch_band_solve(const DevBuf& dd, const BandView& bv, hipStream_t s);      // dd.sys (+ rhs row) -> dd.x
 void launch_chain_elim(const DevBuf& d, const ChainView& cv, hipStream_t s);
 void launch_chain_schur(const DevBuf& d, const ChainView& cv, const DevBuf& dd, hipStream_t s, bool products_done = false);   // writes dd.sys; products_done: W^T W is in dd.wtw (the gather launch formed it)
-// one workgroup of a list-driven block step: block row / column, identity row (-1: a tile of the factorisation proper), flags
-struct TwinTile { int16_t r, c, aj, flags, k, pad; };      // k: the pivot tile of the step this workgroup belongs to      // flags: 1 = writes d.alt instead of d.sys, 2 = no look-ahead on this tile, 4 = c is the step's first trailing column (stores the finished panel block),
-                                                   // 8 = add d.alt's tile to the old value first, 16 = this (diagonal) tile is the next pivot: factor it here,
-                                                   // 32 = with 1 / 8: d.alt2 instead of d.alt (second stage of a nested plan)
 struct TwinView {
-    int T, m0, nchains, nlaunch;   // tiles; first tile of the FINAL dense block (ordinary steps from there); chains; launches of the chain stages
-    const TwinTile* list;          // all launches' tiles: launch t = [off[t], off[t + 1])
-    std::vector<int> off;          // host side
+    int T, final0, nchains, nlaunch;   // tiles; first tile of the FINAL dense block (ordinary steps from there); chains; launches of the chain stages
+    const TwinTile* list;          // all launches' tiles (plba_twin_plan.h): launch t = [off[t], off[t + 1])
+    std::vector<int32_t> off;      // host side
 };
 void launch_twin_cholesky(const DevBuf& d, const TwinView& tv, hipStream_t s);      // sys (permuted; every chain's first tile factored by the producer) -> Lfac, Ninv
 void launch_cholesky(const DevBuf& d, bool use_mfma, int epoch, hipStream_t s, bool tile0_done = false);   // sys -> Lfac (lower) incl. the augmented rows;

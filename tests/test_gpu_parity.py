@@ -671,8 +671,9 @@ def test_ba_call_time_does_not_depend_on_other_problems_alive(pkg, hip):
 @pytest.mark.parametrize("K", [26, 34, 50, 77, 128, 200])
 def test_segment_length_choice_predicts_the_plan_that_is_built(pkg, hip, K):
     """prepare() chooses the chain elimination's segment length by the number of dependent launches the multi-chain factorisation will need
-    (twin_launch_estimate: the plan builder's arithmetic restated for every candidate's dense layout and band).  The estimate for the chosen
-    length must be what the plan that is then BUILT needs — the two pieces of arithmetic are separate code."""
+    (twin_plan_launches of csrc/plba_twin_plan.h, asked for every candidate's dense layout and band).  That count and the plan come from one
+    function now (tests/test_twin_plan_cpu.py holds them together for every T and band); what this test holds is the ROUTE: the tile count
+    and band the segment-length loop predicts for the chosen length must be the ones prepare() then measures and builds the plan for."""
     w = pkg.window.make_window(K, 12 * K, 3 * K, imu=True, seed=0xC0DE + K)
     g = pkg.new_problem(); g.upload_window(w); g.optimize(1)
     assert int(g.debug_get("twin")[0]) == 1
