@@ -156,10 +156,16 @@ def test_device_lba_single_steps_match_the_oracle(pkg, orc, hip):
 
 @pytest.mark.gpu
 def test_device_lba_larger_window_properties(pkg, hip):
-    """a window the oracle's dense LDL^T (N = 6 Nkf + 3 Np + 6 Nl) would need minutes for: properties only"""
+    """a window the oracle's dense LDL^T (N = 6 Nkf + 3 Np + 6 Nl) would need minutes for: the properties below, and parity with the
+    extended-precision reference's eliminated form (tests/lba_ref.py) after one, two, three passes and for the full run"""
+    from . import lba_ref as LR
     w = pkg.window.make_visual_window(K=20, Np=6000, Nl=1200, n_fixed=2, seed=21)
     g = pkg.new_problem()
+    r64, rw = LR.run(w, np.float64), LR.run(w, LR.wide())
+    for k in (1, 2, 3):
+        LR.hold(_run(g, w, max_iters=k), LR.at(r64, k), LR.at(rw, k), "device", "K=20 6000+1200 %d passes" % k, dict(max_iters=k))
     a = _run(g, w)
+    LR.hold(a, r64, rw, "device", "K=20 6000+1200 all passes")
     assert not a["solver_failed"] and a["updates"] >= 1 and np.isfinite(a["T"]).all() and np.isfinite(a["xyz"]).all()
     fixed = w["kf_loc"] < 0
     assert np.array_equal(a["T"][fixed], w["T_kf_w"][fixed])
