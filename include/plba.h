@@ -280,6 +280,48 @@ int plba_get_trace(plba_problem* p, plba_trace_row* rows, int cap, int* n);
  * covisibility bookkeeping) is host map surgery and stays with the caller.  Returns the number of bad observations. */
 int plba_cull_observations(plba_problem* p, double chi2_thresh, uint8_t* bad_point, uint8_t* bad_line, int* n_point_out, int* n_line_out);
 
+/* ---- structure-only landmark refinement (g2o StructureOnlySolver<PointDoF>::calc, pulled in by include/mapHandler.h:43) ----
+ * Every selected landmark is fitted to the keyframes AS THE DEVICE HOLDS THEM, each by a Levenberg-Marquardt of its own, all of them
+ * in one launch: after plba_slide_window (the added two-view triangulations, before the joint LM sees them), after
+ * plba_optimize_pose_graph moved the keyframes, after plba_gate_outliers / plba_cull_observations took observations away.
+ * Per landmark, over its level-0 observations in upload order (e the residual, J its Jacobian with respect to the landmark):
+ *   s = inv_sigma2 e^T e;  chi2 = sum rho(s) (Huber with the kind's delta while the kind's robust switch is on, else s);
+ *   H = sum w J^T J, b = -sum w J^T e, w = rho'(s) inv_sigma2;  mu = lambda_init, nu = 2;
+ *   per iteration up to max_trials trials (H + mu I) delta = b — a point one 3 x 3 system, a line one per end point under one mu,
+ *   chi2 and decision; a pivot <= 0 is a rejected trial —, x' = x + delta, rho = (chi2 - chi2') / (delta^T (mu delta + b));
+ *   rho > 0 with rho and chi2' finite: x = x', chi2 = chi2', mu *= max(1/3, 1 - (2 rho - 1)^3), nu = 2, next iteration;
+ *   otherwise mu *= nu, nu *= 2, next trial.  There is no convergence threshold and no other exit.
+ * The call works on the resident window (a fresh upload, a slid window, the state an optimize left; a changed window is built first,
+ * as plba_recompute_errors builds it).  Keyframes, the estimates of landmarks that are not refined, levels, robust switches, prior,
+ * trace and the plba_save_state copy are untouched.  It ends with the evaluation pass of plba_recompute_errors: plba_get_edge_chi2 and
+ * plba_cull_observations describe the state it leaves.  Two calls from the same state give the same bits.
+ * Refused, the window left as it was: max_iters < 1, max_trials < 1, lambda_init not a positive finite number, no options:
+ * PLBA_ERR_INVALID; a sharded problem (plba_set_shard, world > 1): PLBA_ERR_INVALID; nothing uploaded: PLBA_ERR_STATE. */
+#define PLBA_REFINE_DONE 0        /* ran all iterations                                                          */
+#define PLBA_REFINE_EXHAUSTED 1   /* an iteration found no acceptable trial; keeps its last accepted estimate    */
+#define PLBA_REFINE_NONFINITE 2   /* chi2 was not finite at entry; untouched                                     */
+#define PLBA_REFINE_FIXED 3       /* a fixed landmark; untouched                                                 */
+#define PLBA_REFINE_UNSELECTED 4  /* masked out by select_point / select_line; untouched                         */
+#define PLBA_REFINE_NO_OBS 5      /* no level-0 observation; untouched                                           */
+typedef struct {
+    int    max_iters;        /* LM iterations per landmark                              (5)    */
+    int    max_trials;       /* damped trials per iteration                             (10)   */
+    double lambda_init;      /* initial damping mu of every landmark                    (1e-2) */
+    const uint8_t* select_point;  /* [Np] 1 = refine; NULL = every point               */
+    const uint8_t* select_line;   /* [Nl]                                               */
+    uint8_t* status;         /* optional out [Np + Nl], points then lines: PLBA_REFINE_* */
+    int32_t* iters;          /* optional out [Np + Nl]: iterations whose step was accepted */
+    int32_t* trials;         /* optional out [Np + Nl]: trial solves (a trial refused for its pivot counts) */
+} plba_refine_options;
+typedef struct {
+    int n_refined, n_skipped, n_exhausted;   /* refined = DONE + EXHAUSTED + NONFINITE; skipped = fixed + unselected + no active observation */
+    long long iterations, trials;
+    double chi2_before, chi2_after;          /* robustified, summed over the DONE and EXHAUSTED landmarks in landmark order */
+    double ms_total;
+} plba_refine_stats;
+void plba_refine_default_options(plba_refine_options* o);
+int  plba_refine_landmarks(plba_problem* p, const plba_refine_options* opt, plba_refine_stats* out);
+
 /* ---- dense symmetric positive definite solve on the device (K7 stand-alone) ------------------------------------------
  * Solves A x = b for an n x n row-major A with the kernels plba_optimize uses for the reduced camera system (block
  * LL^T on the fp64 matrix cores + back-substitution): what g2o's LinearSolverEigen / LinearSolverCholmod do for the

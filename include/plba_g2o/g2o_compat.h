@@ -43,6 +43,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -283,6 +284,8 @@ class SparseOptimizer;
 // seven arrays after each optimize().
 inline void plba_sync_estimates(SparseOptimizer* g);
 inline void plba_sync_chi2(SparseOptimizer* g);
+// StructureOnlySolver<PointDoF>::calc: plba_refine_landmarks on the graph the vertices belong to; throws on anything it cannot do
+inline void plba_structure_only(SparseOptimizer* g, const std::vector<void*>& vertices, int point_dof, int num_iters, int num_max_trials);
 // Flatten-at-insertion (round 5): addEdge() copies a point / line observation into the graph's SoA arrays while the object is hot, so that
 // optimize() hands contiguous arrays to the C ABI instead of walking 120 k objects; what the call site changes AFTERWARDS reaches the
 // arrays through these hooks (setLevel, setRobustKernel: written through; anything else: the arrays are rebuilt from the objects).
@@ -487,7 +490,26 @@ public:
 typedef BlockSolver<BlockSolverTraits<6, 3>> BlockSolver_6_3;
 typedef BlockSolver<BlockSolverTraits<7, 3>> BlockSolver_7_3;
 typedef BlockSolver<BlockSolverTraits<3, 2>> BlockSolver_3_2;
-template <int PointDoF> class StructureOnlySolver { public: void calc(...) {} };                 // g2o/solvers/structure_only (included, never used by src/)
+// g2o/solvers/structure_only (pulled in by include/mapHandler.h:43): every landmark vertex of the container is fitted to the keyframes as
+// they are, each by its own Levenberg-Marquardt — on the device, plba_refine_landmarks (include/plba.h).  PointDoF 3: VertexLMPointXYZ,
+// 6: VertexLine.  The vertices must belong to ONE optimizer whose edges are the local-BA family; anything else throws std::runtime_error
+// after the facade's message on std::cerr (the stub this replaces returned the landmarks unchanged without a word).
+template <int PointDoF> class StructureOnlySolver {
+public:
+    static_assert(PointDoF == 3 || PointDoF == 6, "StructureOnlySolver: 3 (VertexLMPointXYZ) or 6 (VertexLine)");
+    template <class VertexContainer>
+    void calc(VertexContainer& vertices, int num_iters, int num_max_trials = 10) {
+        std::vector<void*> vs;
+        SparseOptimizer* g = nullptr;
+        for (auto* v : vertices) {
+            OptimizableGraph::Vertex* bv = v;
+            if (!bv || !bv->graph() || (g && bv->graph() != g)) plba_structure_only(nullptr, vs, PointDoF, num_iters, num_max_trials);
+            g = bv->graph();
+            vs.push_back(bv);
+        }
+        if (!vs.empty()) plba_structure_only(g, vs, PointDoF, num_iters, num_max_trials);
+    }
+};
 class OptimizationAlgorithm { public: virtual ~OptimizationAlgorithm() {} };
 class OptimizationAlgorithmLevenberg : public OptimizationAlgorithm {
 public:
@@ -1092,6 +1114,32 @@ public:
         return _stats.iterations;
     }
 
+    // = g2o StructureOnlySolver::calc for landmark vertices of this graph: uploads the graph if it changed (as optimize() does), refines
+    // the listed landmarks on the device with the keyframes held, and marks the write-back pending (estimates and cached errors)
+    bool refineLandmarks(const std::vector<void*>& vertices, int point_dof, int num_iters, int num_max_trials) {
+        if (!onDevicePath()) return fail("StructureOnlySolver::calc: the graph holds edges outside the local-BA family of the device path");
+        for (void* p : vertices) {
+            const auto* v = static_cast<const OptimizableGraph::Vertex*>(p);
+            if (v->plbaVertexKind() != (point_dof == 3 ? PLBA_V_POINT : PLBA_V_LINE))
+                return fail("StructureOnlySolver<" + std::to_string(point_dof) + ">::calc: vertex " + std::to_string(v->id()) + " is not a " + (point_dof == 3 ? "VertexLMPointXYZ" : "VertexLine"));
+        }
+        if (!flatten()) return false;
+        std::vector<uint8_t> sp(_pts.size() + 1, 0), sl(_lns.size() + 1, 0);
+        for (void* p : vertices) {
+            const auto* v = static_cast<const OptimizableGraph::Vertex*>(p);
+            std::vector<uint8_t>& m = point_dof == 3 ? sp : sl;
+            if (v->_plba_index < 0 || (size_t)v->_plba_index + 1 >= m.size()) return fail("StructureOnlySolver::calc: vertex " + std::to_string(v->id()) + " has no slot in the uploaded window");
+            m[v->_plba_index] = 1;
+        }
+        plba_refine_options o;
+        plba_refine_default_options(&o);
+        o.max_iters = num_iters; o.max_trials = num_max_trials;
+        o.select_point = sp.data(); o.select_line = sl.data();
+        if (plba_refine_landmarks(_prob, &o, &_refine_stats) != PLBA_OK) return fail(plba_last_error(_prob));
+        _stale_est = true; _stale_chi = true;
+        return true;
+    }
+    const plba_refine_stats& lastRefineStats() const { return _refine_stats; }
 
     // ================================================================================================================
     // host path: graphs of host-evaluated edge types (IMUInitEstBg, pose-graph optimisation: SURVEY §8f row 4)
@@ -1619,6 +1667,7 @@ public:
     }
 private:
     bool _stale_est = false, _stale_chi = false;
+    plba_refine_stats _refine_stats{};
     size_t _n_host_edges = 0;
     bool _soa_ok = true, _uploaded_once = false, _ids_ascending = true, _two_priors = false, _lv_touched = true, _rk_touched = true;
     int _level_sent = -1;
@@ -1686,6 +1735,12 @@ inline void EdgeNavStateLine::computeError() {
 inline bool EdgeNavStatePVRPointXYZ::_depth_cache_fresh() { if (_plba_stale && *_plba_stale) plba_sync_chi2(_graph); return _graph ? plba_cached_depth(_graph, _plba_kind, _plba_index, _depth_cache) : _depth_cache; }
 inline bool EdgeNavStateLine::_depth_cache_fresh() { if (_plba_stale && *_plba_stale) plba_sync_chi2(_graph); return _graph ? plba_cached_depth(_graph, _plba_kind, _plba_index, _depth_cache) : _depth_cache; }
 inline void plba_sync_estimates(SparseOptimizer* g) { if (g) g->syncEstimates(); }
+inline void plba_structure_only(SparseOptimizer* g, const std::vector<void*>& vertices, int point_dof, int num_iters, int num_max_trials) {
+    std::string err = "StructureOnlySolver::calc: the vertices belong to no optimizer, or to more than one";
+    if (g) { if (g->refineLandmarks(vertices, point_dof, num_iters, num_max_trials)) return; err = g->lastError(); }
+    std::cerr << "[plba g2o facade] " << err << std::endl;
+    throw std::runtime_error(err);
+}
 inline void plba_sync_chi2(SparseOptimizer* g) { if (g) g->syncChi2(); }
 
 }  // namespace g2o

@@ -83,6 +83,20 @@ class PoseGraph(C.Structure):
                 ("meas12", c_double_p), ("info36", c_double_p)]
 
 
+class RefineOptions(C.Structure):
+    """plba_refine_options of include/plba.h"""
+    _fields_ = [("max_iters", C.c_int), ("max_trials", C.c_int), ("lambda_init", C.c_double), ("select_point", c_uint8_p), ("select_line", c_uint8_p),
+                ("status", c_uint8_p), ("iters", c_int32_p), ("trials", c_int32_p)]
+
+
+class RefineStats(C.Structure):
+    """plba_refine_stats of include/plba.h"""
+    _fields_ = [("n_refined", C.c_int), ("n_skipped", C.c_int), ("n_exhausted", C.c_int), ("iterations", C.c_longlong), ("trials", C.c_longlong),
+                ("chi2_before", C.c_double), ("chi2_after", C.c_double), ("ms_total", C.c_double)]
+
+
+REFINE_DONE, REFINE_EXHAUSTED, REFINE_NONFINITE, REFINE_FIXED, REFINE_UNSELECTED, REFINE_NO_OBS = range(6)
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
 
 _P = C.c_void_p  # plba_problem*
@@ -90,8 +104,10 @@ _P = C.c_void_p  # plba_problem*
 # entry points of the product that have no counterpart in the reference's algorithm (memory management of the device-resident window): the
 # CPU oracle — a restatement of the reference — does not implement them
 # (compute_marginals: the reference computes no marginals; the oracle has no such entry.  optimize_pose_graph: the oracle restates the
-# pose graph as orc_pgo, a checker entry of its own outside this table)
-PRODUCT_ONLY = {"slide_window", "get_sizes", "marginalize_to_prior", "get_prior", "compute_marginals", "optimize_pose_graph"}
+# pose graph as orc_pgo, a checker entry of its own outside this table.  refine_landmarks: g2o's structure-only solver is a stub at the
+# reference's boundary; its checker is the numpy restatement tests/refine_ref.py)
+PRODUCT_ONLY = {"slide_window", "get_sizes", "marginalize_to_prior", "get_prior", "compute_marginals", "optimize_pose_graph",
+                "refine_default_options", "refine_landmarks"}
 
 # name -> (restype, argtypes); every symbol plba.h declares
 SIGNATURES = {
@@ -143,6 +159,8 @@ SIGNATURES = {
     "debug_get": (C.c_int, [_P, C.c_char_p, c_double_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "dense_solve": (C.c_int, [_P, C.c_int, c_double_p, c_double_p, c_double_p, C.POINTER(C.c_int)]),
     "debug_dense_solve": (C.c_int, [_P, C.c_int, c_double_p, c_double_p, c_double_p, C.POINTER(C.c_int)]),
+    "refine_default_options": (None, [C.POINTER(RefineOptions)]),
+    "refine_landmarks": (C.c_int, [_P, C.POINTER(RefineOptions), C.POINTER(RefineStats)]),
     "optimize_pose_graph": (C.c_int, [_P, C.POINTER(PoseGraph), C.c_int, C.c_double, C.c_int, C.POINTER(Stats), C.POINTER(TraceRow), C.c_int, C.POINTER(C.c_int)]),
 }
 
@@ -592,6 +610,32 @@ class Problem:
         trace = [dict(iteration=r.iteration, trial=r.trial, accepted=r.accepted, solver_ok=r.solver_ok, lam=r.lam, chi2_current=r.chi2_current,
                       chi2_trial=r.chi2_trial, scale=r.scale, rho=r.rho) for r in rows[:min(ntr.value, cap)]]
         return X, stats, trace
+
+    def refine_landmarks(self, select_point=None, select_line=None, **opts):
+        """plba_refine_landmarks: every selected landmark fitted to the keyframes the device holds (structure-only LM, one launch).
+        select_point / select_line: boolean masks or None (all); opts: max_iters, max_trials, lambda_init.  Returns a dict of the
+        call's plba_refine_stats plus status / iters / trials, one entry per landmark (points, then lines)."""
+        o = RefineOptions()
+        self.lib.fn["refine_default_options"](C.byref(o))
+        for k, v in opts.items():
+            if k not in ("max_iters", "max_trials", "lambda_init"):
+                raise TypeError("unknown refine option %r" % k)
+            setattr(o, k, v)
+        sz = np.zeros(6, np.int32)
+        self.call("get_sizes", _ip(sz))
+        Np, Nl = int(sz[1]), int(sz[2])
+        sp = None if select_point is None else _u8(np.asarray(select_point).astype(bool))
+        sl = None if select_line is None else _u8(np.asarray(select_line).astype(bool))
+        if (sp is not None and sp.size != Np) or (sl is not None and sl.size != Nl):
+            raise ValueError("select masks must have one entry per point / line")
+        status, iters, trials = np.zeros(max(Np + Nl, 1), np.uint8), np.zeros(max(Np + Nl, 1), np.int32), np.zeros(max(Np + Nl, 1), np.int32)
+        o.select_point, o.select_line = _up(sp), _up(sl)
+        o.status, o.iters, o.trials = _up(status), _ip(iters), _ip(trials)
+        st = RefineStats()
+        self.call("refine_landmarks", C.byref(o), C.byref(st))
+        return dict(n_refined=st.n_refined, n_skipped=st.n_skipped, n_exhausted=st.n_exhausted, iterations=st.iterations, trials=st.trials,
+                    chi2_before=st.chi2_before, chi2_after=st.chi2_after, ms_total=st.ms_total,
+                    status=status[:Np + Nl], iters=iters[:Np + Nl], trials_per_landmark=trials[:Np + Nl])
 
     def preintegrate(self, sample_start, t, gyr, acc, t_prev, t_curr, bg, ba, gyr_meas_cov, acc_meas_cov):
         """KeyFrame::ComputeIMUPreIntSinceLastFrame for M intervals (plba_preintegrate); time stamps as np.longdouble."""

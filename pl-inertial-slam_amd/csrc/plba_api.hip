@@ -2194,6 +2194,71 @@ int plba_recompute_errors(plba_problem* p) {
     return PLBA_OK;
 }
 
+void plba_refine_default_options(plba_refine_options* o) {
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->max_iters = 5; o->max_trials = 10; o->lambda_init = 1e-2;
+}
+// The kernel and its mapping: plba_refine.hip.  Here: the checks, the masks in, one launch, the evaluation pass, the per-landmark words out.
+int plba_refine_landmarks(plba_problem* p, const plba_refine_options* opt, plba_refine_stats* out) {
+    if (!p) return PLBA_ERR_INVALID;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!opt) FAIL(p, PLBA_ERR_INVALID, "plba_refine_landmarks: no plba_refine_options");
+    if (opt->max_iters < 1 || opt->max_trials < 1 || !(opt->lambda_init > 0.0) || !std::isfinite(opt->lambda_init))
+        FAIL(p, PLBA_ERR_INVALID, "plba_refine_landmarks: max_iters %d, max_trials %d, lambda_init %g (need >= 1, >= 1, a positive finite number)", opt->max_iters, opt->max_trials, opt->lambda_init);
+    if (p->world > 1) FAIL(p, PLBA_ERR_INVALID, "plba_refine_landmarks: a sharded problem (plba_set_shard, world %d) is not refined on the device", p->world);
+    if (!p->win.have_cam || !p->win.K) FAIL(p, PLBA_ERR_STATE, "plba_refine_landmarks: nothing uploaded");
+    int rc = prepare(p);
+    if (rc) return rc;
+    HIPCK(p, hipSetDevice(p->device));
+    const int Np = p->win.Np, Nl = p->win.Nl, L = Np + Nl;
+    plba_refine_stats st;
+    memset(&st, 0, sizeof st);
+    if (L > 0) {
+        DArr<uint8_t> d_sel;
+        DArr<double> d_chi;
+        DArr<int32_t> d_cnt;
+        HIPCK(p, d_chi.alloc(2 * (size_t)L, false)); HIPCK(p, d_cnt.alloc(3 * (size_t)L, false));
+        if (opt->select_point || opt->select_line) {
+            std::vector<uint8_t> sel((size_t)L, 1);
+            if (opt->select_point) for (int i = 0; i < Np; ++i) sel[i] = opt->select_point[i] ? 1 : 0;
+            if (opt->select_line) for (int i = 0; i < Nl; ++i) sel[(size_t)Np + i] = opt->select_line[i] ? 1 : 0;
+            HIPCK(p, d_sel.alloc((size_t)L, false));
+            HIPCK(p, plba_h2d(p, d_sel.p, sel.data(), (size_t)L));
+        }
+        RefineArgs a{};
+        a.max_iters = opt->max_iters; a.max_trials = opt->max_trials; a.cur = p->cur; a.lambda_init = opt->lambda_init;
+        a.select = d_sel.p; a.lm_pos = p->lm_grouped ? p->d_lm_pos.p : nullptr; a.chi = d_chi.p; a.cnt = d_cnt.p;
+        ++p->state_epoch;      // (the getters' mirror is of the previous estimates)
+        HIPCK(p, launch_refine(p->dv, p->rob, a, p->stream));
+        launch_linearize(p->dv, p->cur, false, p->rob, owns_pose_edges(p), p->stream);      // the evaluation pass of plba_recompute_errors
+        p->lm_chi_dirty = false;
+        std::vector<double> chi(2 * (size_t)L);
+        std::vector<int32_t> cnt(3 * (size_t)L);
+        HIPCK(p, plba_d2h(p, chi.data(), d_chi.p, chi.size() * sizeof(double)));      // (waits for the stream: the local buffers may go back to the pool)
+        HIPCK(p, plba_d2h(p, cnt.data(), d_cnt.p, cnt.size() * sizeof(int32_t)));
+        for (int i = 0; i < L; ++i) {
+            const int s = cnt[3 * (size_t)i];
+            if (opt->status) opt->status[i] = (uint8_t)s;
+            if (opt->iters) opt->iters[i] = cnt[3 * (size_t)i + 1];
+            if (opt->trials) opt->trials[i] = cnt[3 * (size_t)i + 2];
+            if (s == PLBA_REFINE_FIXED || s == PLBA_REFINE_UNSELECTED || s == PLBA_REFINE_NO_OBS) { ++st.n_skipped; continue; }
+            ++st.n_refined;
+            st.iterations += cnt[3 * (size_t)i + 1]; st.trials += cnt[3 * (size_t)i + 2];
+            if (s == PLBA_REFINE_NONFINITE) continue;
+            if (s == PLBA_REFINE_EXHAUSTED) ++st.n_exhausted;
+            st.chi2_before += chi[2 * (size_t)i]; st.chi2_after += chi[2 * (size_t)i + 1];
+        }
+    } else {
+        launch_linearize(p->dv, p->cur, false, p->rob, owns_pose_edges(p), p->stream);
+        p->lm_chi_dirty = false;
+        HIPCK(p, plba_stream_wait(p, p->stream));
+    }
+    st.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (out) *out = st;
+    return PLBA_OK;
+}
+
 int plba_set_levels(plba_problem* p, plba_edge_kind kind, const uint8_t* level) {
     if (!p || !level) return PLBA_ERR_INVALID;
     if (kind != PLBA_EDGE_POINT && kind != PLBA_EDGE_LINE) FAIL(p, PLBA_ERR_INVALID, "levels only for point/line edges");

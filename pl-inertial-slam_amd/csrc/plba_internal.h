@@ -298,6 +298,17 @@ int marginalize_device(struct plba_problem* p, int first_kf, int max_edges, plba
 int marginalize_factors_device(struct plba_problem* p, const std::vector<int>& imu_edges, const std::vector<int>& pt_edges,
                                const std::vector<int>& ln_edges, bool use_prior, const std::vector<int>& drop_vid, plba_prior* out);
 int marg_resolve(struct plba_problem* p);
+// structure-only landmark refinement (plba_refine.hip): ONE launch, 8 lanes per landmark; writes the refined estimates into both state images
+constexpr int REFINE_KC_LDS_MAX = 256;      // keyframes whose camera blocks the launch stages in LDS (24 KB); beyond, they are formed from the records through L2
+struct RefineArgs {
+    int max_iters, max_trials, cur;
+    double lambda_init;
+    const uint8_t* select;        // L (points, then lines), null: every landmark
+    const int32_t* lm_pos;        // slot -> position in DevBuf::lm (grouped storage), null: slot order
+    double* chi;                  // out, L x 2: robustified chi2 before / after
+    int32_t* cnt;                 // out, L x 3: PLBA_REFINE_* status, accepted iterations, trial solves
+};
+hipError_t launch_refine(const DevBuf& d, const Robust& rb, const RefineArgs& a, hipStream_t s);
 // marginal covariances at the current estimate (plba_cov.hip); the caller has checked the arguments and prepared the window
 int cov_run(struct plba_problem* p, plba_marginals* m);
 void marg_discard(struct plba_problem* p);

@@ -259,6 +259,7 @@ static int pose_graph(const char* in, const char* out, bool ess_graph = false) {
 }
 
 static int local_ba_with_imu(const char* in, const char* out);
+static int structure_only(const char* in, const char* out, bool bad_vertex);
 static int local_ba_with_imu_and_marg(const char* in, const char* out, double* laps);
 // `scrambled`: the same graph as the default mode, built in an order the call site does not use — landmark vertices in DESCENDING id
 // order, every edge after every vertex and the edges of the landmarks in that descending order too, one measurement set again after
@@ -306,6 +307,8 @@ int main(int argc, char** argv) {
     if (argc >= 4 && !strcmp(argv[1], "late")) { g_late_estimates = true; return local_ba_with_imu_and_marg(argv[2], argv[3], nullptr); }
     if (argc >= 4 && !strcmp(argv[1], "scrambled")) { g_scrambled = true; return local_ba_with_imu_and_marg(argv[2], argv[3], nullptr); }
     if (argc >= 4 && !strcmp(argv[1], "lba")) return visual_lba(argv[2], argv[3]);
+    if (argc >= 4 && !strcmp(argv[1], "structonly")) return structure_only(argv[2], argv[3], false);
+    if (argc >= 4 && !strcmp(argv[1], "structonly_bad")) return structure_only(argv[2], argv[3], true);
     // `time window.bin reps`: one localBundleAdjustmentWithImuAndMarg-shaped call through Boundary 1, `reps` times on fresh optimizers, lap by lap
     // (VERDICT r04 item 1b): graph construction | optimize(5) + gating loop + optimize(10) | marginalization | write-back | optimizer teardown.
     if (argc >= 4 && !strcmp(argv[1], "time")) {
@@ -767,5 +770,107 @@ static int local_ba_with_imu(const char* in, const char* out) {
     wr(o, bad_pt); wr(o, bad_ln);
     fclose(o);
     printf("local_ba_with_imu: gated %d+%d, chi2 %.6f\n", gated_pt, gated_ln, chi2_final);
+    return 0;
+}
+
+// g2o::StructureOnlySolver (include/g2o/solvers/structure_only/structure_only_solver.h, pulled in by include/mapHandler.h:43) on a small
+// graph: the window's keyframes as VertexNavStatePVR (held), its points and lines with their observation edges; calc() on every second
+// point (PointDoF 3) and every second line (6).  Input: the window file of tools/harness_io.py (its IMU part is not used).  Output:
+// [P 3K | q 4K as the vertices hold them | points 3Np | lines 6Nl] after calc.  bad_vertex: calc on a keyframe vertex instead — the
+// facade must throw (exit code 3); 0 would mean it ignored the vertex.
+static int structure_only(const char* in, const char* out, bool bad_vertex) {
+    FILE* f = fopen(in, "rb");
+    if (!f) { perror("window"); return 2; }
+    auto hdr = rd<int32_t>(f, 8);
+    const int K = hdr[0], Np = hdr[1], Nl = hdr[2], Ep = hdr[3], El = hdr[4];
+    auto cam = rd<double>(f, 4); auto Rbcv = rd<double>(f, 9); auto Pbcv = rd<double>(f, 3); auto gwv = rd<double>(f, 3); auto hub = rd<double>(f, 4);
+    auto kf_idx = rd<int32_t>(f, K);
+    auto P = rd<double>(f, 3 * K), V = rd<double>(f, 3 * K), q = rd<double>(f, 4 * K), bg = rd<double>(f, 3 * K), ba = rd<double>(f, 3 * K);
+    auto pts = rd<double>(f, 3 * (size_t)Np), lns = rd<double>(f, 6 * (size_t)Nl);
+    auto po_pt = rd<int32_t>(f, Ep), po_kf = rd<int32_t>(f, Ep); auto po_uv = rd<double>(f, 2 * (size_t)Ep), po_sig = rd<double>(f, Ep);
+    auto lo_ln = rd<int32_t>(f, El), lo_kf = rd<int32_t>(f, El); auto lo_l = rd<double>(f, 3 * (size_t)El), lo_sig = rd<double>(f, El);
+    fclose(f);
+    (void)gwv; (void)bg; (void)ba;
+    Matrix3d Rbc; Vector3d tbc;
+    for (int i = 0; i < 3; ++i) { tbc(i) = Pbcv[i]; for (int j = 0; j < 3; ++j) Rbc(i, j) = Rbcv[i * 3 + j]; }
+    const double fx = cam[0], fy = cam[1], cx = cam[2], cy = cam[3];
+    g2o::SparseOptimizer optimizer;
+    auto linearSolver = g2o::make_unique<SlamLinearSolver>();
+    auto blockSolver = g2o::make_unique<g2o::BlockSolverX>(std::move(linearSolver));
+    optimizer.setAlgorithm(new g2o::OptimizationAlgorithmLevenberg(std::move(blockSolver)));
+    int maxKFid = 0;
+    for (int k = 0; k < K; ++k) {
+        NavState ns;
+        ns.Set_Pos(Vector3d(P[3 * k], P[3 * k + 1], P[3 * k + 2])); ns.Set_Vel(Vector3d(V[3 * k], V[3 * k + 1], V[3 * k + 2]));
+        ns.Set_Rot(Sophus::SO3(Quaterniond(q[4 * k + 3], q[4 * k], q[4 * k + 1], q[4 * k + 2])));
+        g2o::VertexNavStatePVR* v = new g2o::VertexNavStatePVR();
+        v->setEstimate(ns); v->setId(kf_idx[k] * 2); v->setFixed(k == 0);
+        optimizer.addVertex(v);
+        maxKFid = std::max(maxKFid, kf_idx[k] * 2 + 1);
+    }
+    std::vector<g2o::OptimizableGraph::Vertex*> sel_pt, sel_ln, sel_bad;
+    int e = 0;
+    for (int l = 0; l < Np; ++l) {
+        g2o::VertexLMPointXYZ* vPoint = new g2o::VertexLMPointXYZ();
+        vPoint->setEstimate(Vector3d(pts[3 * l], pts[3 * l + 1], pts[3 * l + 2]));
+        const int id = l + maxKFid + 1;
+        vPoint->setId(id); vPoint->setMarginalized(true);
+        optimizer.addVertex(vPoint);
+        if (l % 2 == 0) sel_pt.push_back(vPoint);
+        for (; e < Ep && po_pt[e] == l; ++e) {
+            g2o::EdgeNavStatePVRPointXYZ* ed = new g2o::EdgeNavStatePVRPointXYZ();
+            ed->setVertex(0, optimizer.vertex(id)); ed->setVertex(1, optimizer.vertex(2 * kf_idx[po_kf[e]]));
+            ed->setMeasurement(Vector2d(po_uv[2 * e], po_uv[2 * e + 1]));
+            const float invSigma2 = 1.0 / po_sig[e];
+            ed->setInformation(Eigen::Matrix2d::Identity() * invSigma2);
+            g2o::RobustKernelHuber* rk = new g2o::RobustKernelHuber; ed->setRobustKernel(rk); rk->setDelta(hub[0]);
+            ed->SetParams(fx, fy, cx, cy, Rbc, tbc);
+            optimizer.addEdge(ed);
+        }
+    }
+    const int maxPointId = Np + maxKFid + 1;
+    e = 0;
+    for (int l = 0; l < Nl; ++l) {
+        g2o::VertexLine* vLine = new g2o::VertexLine();
+        Vector6d l6; for (int c = 0; c < 6; ++c) l6(c) = lns[6 * l + c];
+        vLine->setEstimate(l6);
+        const int id = l + maxPointId + 1;
+        vLine->setId(id); vLine->setMarginalized(true);
+        optimizer.addVertex(vLine);
+        if (l % 2 == 0) sel_ln.push_back(vLine);
+        for (; e < El && lo_ln[e] == l; ++e) {
+            g2o::EdgeNavStateLine* ed = new g2o::EdgeNavStateLine();
+            ed->setVertex(0, optimizer.vertex(id)); ed->setVertex(1, optimizer.vertex(2 * kf_idx[lo_kf[e]]));
+            ed->setMeasurement(Vector3d(lo_l[3 * e], lo_l[3 * e + 1], lo_l[3 * e + 2]));
+            const float invSigma2 = 1.0 / lo_sig[e];
+            ed->setInformation(Eigen::Matrix3d::Identity() * invSigma2);
+            g2o::RobustKernelHuber* rk = new g2o::RobustKernelHuber; ed->setRobustKernel(rk); rk->setDelta(hub[1]);
+            ed->SetParams(fx, fy, cx, cy, Rbc, tbc);
+            optimizer.addEdge(ed);
+        }
+    }
+    optimizer.initializeOptimization();
+    g2o::StructureOnlySolver<3> structure_only_ba;
+    g2o::StructureOnlySolver<6> structure_only_lines;
+    if (bad_vertex) {
+        sel_bad.push_back(optimizer.vertex(2 * kf_idx[K - 1]));
+        try { structure_only_ba.calc(sel_bad, 3); } catch (const std::exception& ex) { fprintf(stderr, "structonly_bad: refused: %s\n", ex.what()); return 3; }
+        return 0;
+    }
+    structure_only_ba.calc(sel_pt, 3);
+    structure_only_lines.calc(sel_ln, 3, 10);
+    std::vector<double> oP(3 * K), oq(4 * K), opts(3 * (size_t)Np), olns(6 * (size_t)Nl);
+    for (int k = 0; k < K; ++k) {
+        const NavState& a = static_cast<g2o::VertexNavStatePVR*>(optimizer.vertex(2 * kf_idx[k]))->estimate();
+        std::memcpy(&oP[3 * k], a.raw(), 24); std::memcpy(&oq[4 * k], a.raw() + 6, 32);
+    }
+    for (int l = 0; l < Np; ++l) { const Vector3d& p = static_cast<g2o::VertexLMPointXYZ*>(optimizer.vertex(l + maxKFid + 1))->estimate(); for (int i = 0; i < 3; ++i) opts[3 * l + i] = p(i); }
+    for (int l = 0; l < Nl; ++l) { const Vector6d& p = static_cast<g2o::VertexLine*>(optimizer.vertex(l + maxPointId + 1))->estimate(); for (int i = 0; i < 6; ++i) olns[6 * l + i] = p(i); }
+    FILE* o = fopen(out, "wb");
+    if (!o) { perror("result"); return 2; }
+    wr(o, oP); wr(o, oq); wr(o, opts); wr(o, olns);
+    fclose(o);
+    const plba_refine_stats& st = optimizer.lastRefineStats();
+    printf("structure_only: %zu points + %zu lines refined, last call chi2 %.6f -> %.6f\n", sel_pt.size(), sel_ln.size(), st.chi2_before, st.chi2_after);
     return 0;
 }
