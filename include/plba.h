@@ -515,6 +515,66 @@ typedef struct plba_pose_graph {
 int plba_optimize_pose_graph(plba_problem* p, plba_pose_graph* g, int max_iters, double user_lambda_init, int initial_guess,
                              plba_stats* stats, plba_trace_row* trace, int trace_cap, int* n_trace);
 
+/* ---- loop-closure candidate verification: batched relative pose ------------------------------------
+ * MapHandler::isLoopClosure's numeric step, computeRelativePoseRobustGN (src/mapHandler.cpp:3675-4066; protocol 0) or the plain
+ * computeRelativePoseGN (:3411-3673; protocol 1), for B candidates in ONE launch, one wave per candidate: a Gauss-Newton on one SE(3)
+ * increment T_inc over matched stereo points (P3 in the frame of kf0, uv2 observed in kf1) and line segments (sPeP6, the observed
+ * line l3 = le_obs) with scalar residuals (the norm of the reprojection error) and Cauchy weights, the sqrt(chi2_th) outlier cut and
+ * (protocol 0) a refinement on the inliers; then the reference's decision.  Semantics, literally as coded there:
+ *   a pass zeroes H, g and e, runs over the inlier points, then the inlier lines, and sets e /= (N_p + N_l);
+ *   exit tests |e - err_prev| < eps or e < eps before the solve, |x_inc| < eps after the update (eps = DBL_EPSILON);
+ *   H x_inc = g by column-pivoted Householder QR (Eigen's ColPivHouseholderQR as documented: pivoting by the largest remaining column
+ *   norm, rank threshold eps 6 |largest pivot|, zeros for the deficient part);  T_inc = T_inc inverse_se3(expmap_se3(x_inc));
+ *   H and e reported are those of the LAST PASS EVALUATED, not of the pose after the last step (no pass at all: zeros);
+ *   protocol 0 carries err_prev from the first stage into the refinement, forces lc_inl (:4012) and returns
+ *   pose_inc = logmap(inverse(expmap(logmap(T_inc)))) (:4060); protocol 1 has no refinement, applies lc_inl and returns
+ *   logmap(inverse(T_inc)) (:3667);  the cut compares the UNWEIGHTED error norm with sqrt(chi2_th);
+ *   t = |x.head(3)|, r = |x.tail(3)| 180 / pi of x = logmap_se3(T_inc);  DT_cov = H^-1, cov_eig6 its eigenvalues, ascending;
+ *   accepted = lc_res (e < lc_res) && lc_unc (cov_eig6[5] < lc_unc) && lc_inl (inliers / features > lc_inl) && lc_trs && lc_rot.
+ * Input, CSR over the candidates: candidate b owns the points [pt_start[b], pt_start[b+1]) and the lines [ln_start[b], ln_start[b+1]).
+ * T0_16 (optional): B row-major 4 x 4 start increments; NULL = identity, as the reference starts.  pt_inlier / ln_inlier (optional,
+ * in/out, one byte per feature): in = the features to use (NULL = all, as PointFeature / LineFeature are constructed), out = what the
+ * cut left.  out: B results.  pose_inc6 is filled for status OK and RANK whether or not the candidate is accepted.
+ * Deviations: no inlier at the entry of a stage: PLBA_RELPOSE_EMPTY, T_inc as it stood (the reference divides by
+ * zero); a non-finite e: PLBA_RELPOSE_NONFINITE; H not of full rank by the rule above: PLBA_RELPOSE_RANK, cov_eig6 = +inf, lc_unc
+ * fails (the reference inverts regardless).  None of the three is accepted; EMPTY and NONFINITE report no decision bit.
+ * Refused with PLBA_ERR_INVALID and every output untouched: B < 1, starts that do not begin at 0 or descend, a missing array whose
+ * count is non-zero, a missing output or options, non-finite input, protocol not 0 or 1, a negative iteration count or chi2_th.
+ * `p` supplies the device, the stream and the error text; the uploaded window, prior, trace and saved state are neither read nor
+ * written and nothing needs to be uploaded.  Inputs go up in one staged copy, results come back in one: the call blocks once
+ * (plba_debug_get("host_waits")).  A candidate's result does not depend on B or on its neighbours; two calls give the same bits. */
+#define PLBA_RELPOSE_OK 0
+#define PLBA_RELPOSE_EMPTY 1      /* no inlier feature at the entry of a stage                    */
+#define PLBA_RELPOSE_NONFINITE 2  /* a pass gave a non-finite e                                   */
+#define PLBA_RELPOSE_RANK 3       /* the reported H is rank deficient: no covariance              */
+typedef struct plba_relpose_options {
+    int    max_iters;        /* Config::maxIters      first-stage iterations           (5)     */
+    int    max_iters_ref;    /* Config::maxItersRef   refinement iterations            (10)    */
+    double homog_th;         /* Config::homogTh       floor of gz^2 and of the norm    (1e-7)  */
+    double chi2_th;          /* the cut is sqrt(chi2_th)                               (7.815) */
+    int    protocol;         /* 0 = computeRelativePoseRobustGN, 1 = computeRelativePoseGN     */
+    int    reserved;
+    double lc_res, lc_unc, lc_inl, lc_trs, lc_rot;   /* SlamConfig::lcRes .. lcRot     (1.0, 0.01, 0.3, 1.5, 35.0) */
+} plba_relpose_options;
+typedef struct plba_relpose_result {
+    double  T_inc16[16];     /* row-major 4 x 4                                                 */
+    double  pose_inc6[6];    /* (t, w): the loop edge's increment                               */
+    double  H36[36];         /* row-major, symmetric                                            */
+    double  e;
+    double  cov_eig6[6];     /* ascending; +inf unless status is OK                             */
+    double  t, r;            /* |translation| and rotation angle in degrees of logmap(T_inc)    */
+    int32_t n_inliers;       /* inlier features when the run ended                              */
+    int32_t iters[2];        /* passes evaluated by the first stage / the refinement            */
+    int32_t status;          /* PLBA_RELPOSE_*                                                  */
+    int32_t accepted;
+    int32_t lc_res, lc_unc, lc_inl, lc_trs, lc_rot;
+} plba_relpose_result;
+void plba_relpose_default_options(plba_relpose_options* o);
+int  plba_relative_pose(plba_problem* p, const plba_relpose_options* opt, int B, const int32_t* pt_start, const double* P3,
+                        const double* uv2, const int32_t* ln_start, const double* sPeP6, const double* l3,
+                        double fx, double fy, double cx, double cy, const double* T0_16, uint8_t* pt_inlier, uint8_t* ln_inlier,
+                        plba_relpose_result* out);
+
 /* ---- diagnostics used by the parity tests (not needed by a drop-in caller) ------------------- */
 /* Runs computeActiveErrors + buildSystem + setLambda(lambda) + Schur on the current state without
  * updating it, then exposes named internal buffers: "Hschur" (P*P row-major), "bschur" (P),

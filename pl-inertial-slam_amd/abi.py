@@ -95,6 +95,20 @@ class RefineStats(C.Structure):
                 ("chi2_before", C.c_double), ("chi2_after", C.c_double), ("ms_total", C.c_double)]
 
 
+class RelposeOptions(C.Structure):
+    """plba_relpose_options of include/plba.h"""
+    _fields_ = [("max_iters", C.c_int), ("max_iters_ref", C.c_int), ("homog_th", C.c_double), ("chi2_th", C.c_double), ("protocol", C.c_int),
+                ("reserved", C.c_int), ("lc_res", C.c_double), ("lc_unc", C.c_double), ("lc_inl", C.c_double), ("lc_trs", C.c_double), ("lc_rot", C.c_double)]
+
+
+class RelposeResult(C.Structure):
+    """plba_relpose_result of include/plba.h"""
+    _fields_ = [("T_inc16", C.c_double * 16), ("pose_inc6", C.c_double * 6), ("H36", C.c_double * 36), ("e", C.c_double), ("cov_eig6", C.c_double * 6),
+                ("t", C.c_double), ("r", C.c_double), ("n_inliers", C.c_int32), ("iters", C.c_int32 * 2), ("status", C.c_int32), ("accepted", C.c_int32),
+                ("lc_res", C.c_int32), ("lc_unc", C.c_int32), ("lc_inl", C.c_int32), ("lc_trs", C.c_int32), ("lc_rot", C.c_int32)]
+
+
+RELPOSE_OK, RELPOSE_EMPTY, RELPOSE_NONFINITE, RELPOSE_RANK = range(4)
 REFINE_DONE, REFINE_EXHAUSTED, REFINE_NONFINITE, REFINE_FIXED, REFINE_UNSELECTED, REFINE_NO_OBS = range(6)
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
@@ -105,9 +119,9 @@ _P = C.c_void_p  # plba_problem*
 # CPU oracle — a restatement of the reference — does not implement them
 # (compute_marginals: the reference computes no marginals; the oracle has no such entry.  optimize_pose_graph: the oracle restates the
 # pose graph as orc_pgo, a checker entry of its own outside this table.  refine_landmarks: g2o's structure-only solver is a stub at the
-# reference's boundary; its checker is the numpy restatement tests/refine_ref.py)
+# reference's boundary; its checker is the numpy restatement tests/refine_ref.py.  relative_pose: its checker is tests/relpose_ref.py)
 PRODUCT_ONLY = {"slide_window", "get_sizes", "marginalize_to_prior", "get_prior", "compute_marginals", "optimize_pose_graph",
-                "refine_default_options", "refine_landmarks"}
+                "refine_default_options", "refine_landmarks", "relpose_default_options", "relative_pose"}
 
 # name -> (restype, argtypes); every symbol plba.h declares
 SIGNATURES = {
@@ -161,6 +175,9 @@ SIGNATURES = {
     "debug_dense_solve": (C.c_int, [_P, C.c_int, c_double_p, c_double_p, c_double_p, C.POINTER(C.c_int)]),
     "refine_default_options": (None, [C.POINTER(RefineOptions)]),
     "refine_landmarks": (C.c_int, [_P, C.POINTER(RefineOptions), C.POINTER(RefineStats)]),
+    "relpose_default_options": (None, [C.POINTER(RelposeOptions)]),
+    "relative_pose": (C.c_int, [_P, C.POINTER(RelposeOptions), C.c_int, c_int32_p, c_double_p, c_double_p, c_int32_p, c_double_p, c_double_p,
+                                C.c_double, C.c_double, C.c_double, C.c_double, c_double_p, c_uint8_p, c_uint8_p, C.POINTER(RelposeResult)]),
     "optimize_pose_graph": (C.c_int, [_P, C.POINTER(PoseGraph), C.c_int, C.c_double, C.c_int, C.POINTER(Stats), C.POINTER(TraceRow), C.c_int, C.POINTER(C.c_int)]),
 }
 
@@ -636,6 +653,57 @@ class Problem:
         return dict(n_refined=st.n_refined, n_skipped=st.n_skipped, n_exhausted=st.n_exhausted, iterations=st.iterations, trials=st.trials,
                     chi2_before=st.chi2_before, chi2_after=st.chi2_after, ms_total=st.ms_total,
                     status=status[:Np + Nl], iters=iters[:Np + Nl], trials_per_landmark=trials[:Np + Nl])
+
+    def relative_pose(self, P3, uv, sPeP, l3, cam, T0=None, pt_inlier=None, ln_inlier=None, **opts):
+        """plba_relative_pose: B loop-closure candidates verified in one launch.  P3 / uv / sPeP / l3: lists of B arrays ((n, 3), (n, 2),
+        (m, 6), (m, 3); an empty array or None for a candidate without points or lines); cam = (fx, fy, cx, cy); T0: (B, 4, 4) or None
+        (identity); pt_inlier / ln_inlier: lists of B masks or None (all); opts: the fields of plba_relpose_options.  Returns a dict of
+        arrays over the candidates — T_inc (B, 4, 4), pose_inc (B, 6), H (B, 6, 6), e, cov_eig (B, 6), t, r, n_inliers, iters (B, 2), status,
+        accepted, lc_res .. lc_rot — and pt_inlier / ln_inlier, lists of B boolean masks as the cut left them."""
+        o = RelposeOptions()
+        self.lib.fn["relpose_default_options"](C.byref(o))
+        for k, v in opts.items():
+            if k == "reserved" or not hasattr(o, k):
+                raise TypeError("unknown relative-pose option %r" % k)
+            setattr(o, k, v)
+        B = len(P3)
+        if not (len(uv) == len(sPeP) == len(l3) == B):
+            raise ValueError("P3, uv, sPeP and l3 must list the same candidates")
+
+        def csr(lists, width):
+            arrs = [np.zeros((0, width)) if a is None else _f64(a).reshape(-1, width) for a in lists]
+            start = np.zeros(len(arrs) + 1, np.int32)
+            start[1:] = np.cumsum([len(a) for a in arrs])
+            return start, (np.concatenate(arrs) if arrs else np.zeros((0, width)))
+        ps, P = csr(P3, 3); ps2, U2 = csr(uv, 2); ls, PQ = csr(sPeP, 6); ls2, L3 = csr(l3, 3)
+        if not (np.array_equal(ps, ps2) and np.array_equal(ls, ls2)):
+            raise ValueError("a candidate's P3 / uv or sPeP / l3 differ in length")
+
+        def masks(m, start):
+            if m is None:
+                return np.ones(max(int(start[-1]), 1), np.uint8)
+            if len(m) != B or any(len(np.asarray(a).ravel()) != start[b + 1] - start[b] for b, a in enumerate(m)):
+                raise ValueError("a mask list must have one entry per candidate and one flag per feature")
+            flat = np.concatenate([np.asarray(a).ravel().astype(bool) for a in m]) if B else np.zeros(0, bool)
+            return np.concatenate([flat.astype(np.uint8), np.zeros(1 if flat.size == 0 else 0, np.uint8)])
+        pm, lm = masks(pt_inlier, ps), masks(ln_inlier, ls)
+        T = None if T0 is None else _f64(T0).reshape(-1, 16).copy()
+        if T is not None and T.shape[0] != B:
+            raise ValueError("T0 must be (B, 4, 4)")
+        res = (RelposeResult * max(B, 1))()
+        self.call("relative_pose", C.byref(o), B, _ip(ps), _dp(P) if len(P) else None, _dp(U2) if len(U2) else None, _ip(ls),
+                  _dp(PQ) if len(PQ) else None, _dp(L3) if len(L3) else None, float(cam[0]), float(cam[1]), float(cam[2]), float(cam[3]),
+                  _dp(T), _up(pm), _up(lm), res)
+        out = dict(T_inc=np.array([list(r.T_inc16) for r in res[:B]]).reshape(B, 4, 4), pose_inc=np.array([list(r.pose_inc6) for r in res[:B]]).reshape(B, 6),
+                   H=np.array([list(r.H36) for r in res[:B]]).reshape(B, 6, 6), cov_eig=np.array([list(r.cov_eig6) for r in res[:B]]).reshape(B, 6),
+                   iters=np.array([list(r.iters) for r in res[:B]], np.int32).reshape(B, 2))
+        for k in ("e", "t", "r"):
+            out[k] = np.array([getattr(r, k) for r in res[:B]], np.float64)
+        for k in ("n_inliers", "status", "accepted", "lc_res", "lc_unc", "lc_inl", "lc_trs", "lc_rot"):
+            out[k] = np.array([getattr(r, k) for r in res[:B]], np.int32)
+        out["pt_inlier"] = [pm[ps[b]:ps[b + 1]].astype(bool) for b in range(B)]
+        out["ln_inlier"] = [lm[ls[b]:ls[b + 1]].astype(bool) for b in range(B)]
+        return out
 
     def preintegrate(self, sample_start, t, gyr, acc, t_prev, t_curr, bg, ba, gyr_meas_cov, acc_meas_cov):
         """KeyFrame::ComputeIMUPreIntSinceLastFrame for M intervals (plba_preintegrate); time stamps as np.longdouble."""

@@ -294,6 +294,7 @@ static int vio_init(const char* in, const char* out) {
     return 0;
 }
 
+static int relpose(const char* in, const char* out);
 int main(int argc, char** argv) {
     if (argc >= 4 && !strcmp(argv[1], "gyrbias")) return imu_init_est_bg(argv[2], argv[3]);
     if (argc >= 4 && !strcmp(argv[1], "pgo")) return pose_graph(argv[2], argv[3]);
@@ -307,6 +308,7 @@ int main(int argc, char** argv) {
     if (argc >= 4 && !strcmp(argv[1], "late")) { g_late_estimates = true; return local_ba_with_imu_and_marg(argv[2], argv[3], nullptr); }
     if (argc >= 4 && !strcmp(argv[1], "scrambled")) { g_scrambled = true; return local_ba_with_imu_and_marg(argv[2], argv[3], nullptr); }
     if (argc >= 4 && !strcmp(argv[1], "lba")) return visual_lba(argv[2], argv[3]);
+    if (argc >= 4 && !strcmp(argv[1], "relpose")) return relpose(argv[2], argv[3]);
     if (argc >= 4 && !strcmp(argv[1], "structonly")) return structure_only(argv[2], argv[3], false);
     if (argc >= 4 && !strcmp(argv[1], "structonly_bad")) return structure_only(argv[2], argv[3], true);
     // `time window.bin reps`: one localBundleAdjustmentWithImuAndMarg-shaped call through Boundary 1, `reps` times on fresh optimizers, lap by lap
@@ -872,5 +874,98 @@ static int structure_only(const char* in, const char* out, bool bad_vertex) {
     fclose(o);
     const plba_refine_stats& st = optimizer.lastRefineStats();
     printf("structure_only: %zu points + %zu lines refined, last call chi2 %.6f -> %.6f\n", sel_pt.size(), sel_ln.size(), st.chi2_before, st.chi2_after);
+    return 0;
+}
+
+// MapHandler::isLoopClosure's call site (src/mapHandler.cpp:3301-3409) for B candidates at once: from the matched lists (lc_points, lc_lines
+// with lc_pt_idx, lc_ls_idx, as the two matching loops fill them) to the arrays of plba_relative_pose, through the call, to the decision, the
+// compaction of lc_pt_idx / lc_ls_idx by the masks and pose_inc.  (The reference compacts lc_points twice and lc_lines never, :3662-3665 and
+// :4055-4058; here every list keeps its inliers.)  Input and output: the files of csrc/plba_relpose_hostcheck.cpp, so that the two can be
+// compared; `returned` is isLoopClosure's return value and the masks say which entries of the index lists stayed.
+#include "plba_g2o/relative_pose.h"
+static int relpose(const char* in, const char* out) {
+    FILE* f = fopen(in, "rb");
+    if (!f) { perror("batch"); return 2; }
+    auto hd = rd<int32_t>(f, 6); auto par = rd<double>(f, 11);
+    const int B = hd[0];
+    auto ps = rd<int32_t>(f, (size_t)B + 1), ls = rd<int32_t>(f, (size_t)B + 1);
+    const size_t Np = (size_t)ps[B], Nl = (size_t)ls[B];
+    auto P = rd<double>(f, 3 * Np), uv = rd<double>(f, 2 * Np), pq = rd<double>(f, 6 * Nl), l3 = rd<double>(f, 3 * Nl);
+    std::vector<double> T0; if (hd[4]) T0 = rd<double>(f, 16 * (size_t)B);
+    std::vector<uint8_t> pm(Np, 1), lm(Nl, 1);
+    if (hd[5]) { pm = rd<uint8_t>(f, Np); lm = rd<uint8_t>(f, Nl); }
+    fclose(f);
+    // the matched lists of every candidate, as isLoopClosure builds them
+    std::vector<std::vector<plba_g2o::PointFeature>> lc_points(B);
+    std::vector<std::vector<plba_g2o::LineFeature>> lc_lines(B);
+    std::vector<std::vector<plba_g2o::Vector4i>> lc_pt_idx(B), lc_ls_idx(B);
+    for (int b = 0; b < B; ++b) {
+        for (int k = ps[b]; k < ps[b + 1]; ++k) {
+            plba_g2o::PointFeature pt; std::memcpy(pt.P, &P[3 * (size_t)k], 24); std::memcpy(pt.pl_obs, &uv[2 * (size_t)k], 16); pt.inlier = pm[k] != 0;
+            lc_points[b].push_back(pt); lc_pt_idx[b].push_back({k - ps[b], k - ps[b], k - ps[b], k - ps[b]});
+        }
+        for (int k = ls[b]; k < ls[b + 1]; ++k) {
+            plba_g2o::LineFeature ln; std::memcpy(ln.sP, &pq[6 * (size_t)k], 24); std::memcpy(ln.eP, &pq[6 * (size_t)k + 3], 24); std::memcpy(ln.le_obs, &l3[3 * (size_t)k], 24); ln.inlier = lm[k] != 0;
+            lc_lines[b].push_back(ln); lc_ls_idx[b].push_back({k - ls[b], k - ls[b], k - ls[b], k - ls[b]});
+        }
+    }
+    // lists -> arrays
+    std::vector<int32_t> pt_start(B + 1, 0), ln_start(B + 1, 0);
+    std::vector<double> aP, auv, apq, al3;
+    std::vector<uint8_t> apm, alm;
+    for (int b = 0; b < B; ++b) {
+        for (const auto& pt : lc_points[b]) { aP.insert(aP.end(), pt.P, pt.P + 3); auv.insert(auv.end(), pt.pl_obs, pt.pl_obs + 2); apm.push_back(pt.inlier ? 1 : 0); }
+        for (const auto& ln : lc_lines[b]) { apq.insert(apq.end(), ln.sP, ln.sP + 3); apq.insert(apq.end(), ln.eP, ln.eP + 3); al3.insert(al3.end(), ln.le_obs, ln.le_obs + 3); alm.push_back(ln.inlier ? 1 : 0); }
+        pt_start[b + 1] = (int32_t)apm.size(); ln_start[b + 1] = (int32_t)alm.size();
+    }
+    apm.push_back(0); alm.push_back(0);
+    plba_problem* p = nullptr;
+    if (plba_create(nullptr, &p) != PLBA_OK) { fprintf(stderr, "relpose: %s\n", plba_last_error(nullptr)); return 2; }
+    plba_relpose_options ro; plba_relpose_default_options(&ro);
+    ro.protocol = hd[1]; ro.max_iters = hd[2]; ro.max_iters_ref = hd[3]; ro.homog_th = par[0]; ro.chi2_th = par[1];
+    ro.lc_res = par[2]; ro.lc_unc = par[3]; ro.lc_inl = par[4]; ro.lc_trs = par[5]; ro.lc_rot = par[6];
+    std::vector<plba_relpose_result> res(B);
+    const int rc = plba_relative_pose(p, &ro, B, pt_start.data(), aP.empty() ? nullptr : aP.data(), auv.empty() ? nullptr : auv.data(), ln_start.data(),
+                                      apq.empty() ? nullptr : apq.data(), al3.empty() ? nullptr : al3.data(), par[7], par[8], par[9], par[10],
+                                      hd[4] ? T0.data() : nullptr, apm.data(), alm.data(), res.data());
+    if (rc != PLBA_OK) { fprintf(stderr, "relpose: %s\n", plba_last_error(p)); plba_destroy(p); return 2; }
+    plba_destroy(p);
+    // the decision, the compaction and pose_inc, per candidate
+    std::vector<double> od((size_t)B * 73, 0.0);
+    std::vector<int32_t> oi((size_t)B * 11, 0);
+    std::vector<uint8_t> pmo(Np, 0), lmo(Nl, 0);
+    int n_loops = 0;
+    for (int b = 0; b < B; ++b) {
+        const plba_relpose_result& r = res[b];
+        double pose_inc[6] = {0, 0, 0, 0, 0, 0};
+        for (size_t i = 0; i < lc_points[b].size(); ++i) lc_points[b][i].inlier = apm[(size_t)pt_start[b] + i] != 0;
+        for (size_t i = 0; i < lc_lines[b].size(); ++i) lc_lines[b][i].inlier = alm[(size_t)ln_start[b] + i] != 0;
+        const bool is_loop = r.accepted != 0;
+        if (is_loop) {
+            std::vector<plba_g2o::Vector4i> pi, li;
+            std::vector<plba_g2o::PointFeature> pts; std::vector<plba_g2o::LineFeature> lns;
+            for (size_t i = 0; i < lc_points[b].size(); ++i) if (lc_points[b][i].inlier) { pts.push_back(lc_points[b][i]); pi.push_back(lc_pt_idx[b][i]); }
+            for (size_t i = 0; i < lc_lines[b].size(); ++i) if (lc_lines[b][i].inlier) { lns.push_back(lc_lines[b][i]); li.push_back(lc_ls_idx[b][i]); }
+            lc_points[b].swap(pts); lc_lines[b].swap(lns); lc_pt_idx[b].swap(pi); lc_ls_idx[b].swap(li);
+            std::memcpy(pose_inc, r.pose_inc6, 48);
+            for (const auto& v : lc_pt_idx[b]) pmo[(size_t)ps[b] + (size_t)v[0]] = 1;
+            for (const auto& v : lc_ls_idx[b]) lmo[(size_t)ls[b] + (size_t)v[0]] = 1;
+            ++n_loops;
+        } else {
+            for (size_t i = 0; i < lc_points[b].size(); ++i) pmo[(size_t)ps[b] + i] = lc_points[b][i].inlier ? 1 : 0;
+            for (size_t i = 0; i < lc_lines[b].size(); ++i) lmo[(size_t)ls[b] + i] = lc_lines[b][i].inlier ? 1 : 0;
+        }
+        double* o = &od[(size_t)b * 73];
+        std::memcpy(o, r.T_inc16, 128); std::memcpy(o + 16, r.pose_inc6, 48); std::memcpy(o + 22, r.H36, 288); o[58] = r.e; std::memcpy(o + 59, r.cov_eig6, 48);
+        o[65] = r.t; o[66] = r.r; std::memcpy(o + 67, pose_inc, 48);
+        int32_t* q = &oi[(size_t)b * 11];
+        q[0] = r.n_inliers; q[1] = r.iters[0]; q[2] = r.iters[1]; q[3] = r.status; q[4] = r.accepted; q[5] = r.lc_res; q[6] = r.lc_unc; q[7] = r.lc_inl; q[8] = r.lc_trs;
+        q[9] = r.lc_rot; q[10] = is_loop ? 1 : 0;
+    }
+    FILE* o = fopen(out, "wb");
+    if (!o) { perror("result"); return 2; }
+    wr(o, od); wr(o, oi); wr(o, pmo); wr(o, lmo);
+    fclose(o);
+    printf("relpose: %d of %d candidates are loop closures\n", n_loops, B);
     return 0;
 }
