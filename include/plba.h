@@ -575,6 +575,82 @@ int  plba_relative_pose(plba_problem* p, const plba_relpose_options* opt, int B,
                         double fx, double fy, double cx, double cy, const double* T0_16, uint8_t* pt_inlier, uint8_t* ln_inlier,
                         plba_relpose_result* out);
 
+/* ---- frame-to-frame pose tracking: batched optimizePose ----------------------------------------------
+ * StereoFrameHandler::optimizePose (stvo-pl/src/stereoFrameHandler.cpp:334-419) for B problems in ONE launch, one wave per problem and
+ * the whole protocol of a problem inside the launch: the tracker's estimate of every frame (app/plslam_dataset.cpp:133) and the one
+ * MapHandler::lookForCommonMatches makes for every inserted keyframe (src/mapHandler.cpp:831).  Only mode 0 of :356 is built, the one
+ * the reference compiles in (Gauss-Newton, the robust Gauss-Newton as the fallback); the Levenberg-Marquardt mode (:509-574) is not.
+ * Semantics, literally as coded there:
+ *   a pass (optimizeFunctions, :576-721) runs over the inlier points, then the inlier lines: r = |err| sqrt(sigma2), w = 1 / (1 + r^2),
+ *   lines w *= overlap (StereoFrame::lineSegmentOverlap, stvo-pl/src/stereoFrame.cpp:521-627: the vertical, the horizontal and the
+ *   general branch by |dx| < 1, |dy| < 1 of the observed end points, lambda_s / lambda_e of the projected end points along the observed
+ *   segment, five outcomes); J_aux as :609-615 / :663-683 (fx for both axes, homog_th the floor of gz^2 and of the norm);
+ *   H += J J^T w, g += J r w, e += r^2 w, e /= (N_p + N_l);
+ *   a stage (gaussNewtonOptimization, :421-458): err_prev = 999999999.9; err > err_prev breaks when iters > 0 (the pose keeps the step
+ *   already taken, H and err are those of the worse pass) and otherwise returns err = -1; exit on err < min_error or
+ *   |err - err_prev| < min_error_change before the solve; H x = g by the pivoted QR of plba_relative_pose; DT = DT inverse(expmap(x));
+ *   exit when |x.head(3)| and |x.tail(3)| are both below min_error_change; DT_cov = H^-1;
+ *   the protocol (:359-395): fewer than min_features inliers at entry: identity (path 2).  The first stage runs max_iters passes on a
+ *   COPY of the start pose.  isGoodSolution (:319-332): cov_eig(0) >= 0, cov_eig(5) <= 1, 0 <= err <= 1, DT finite.  Good: the cut
+ *   runs at the first stage's pose, then with at least min_features inliers left the refinement (max_iters_ref) STARTS AGAIN FROM THE
+ *   START POSE (:374 passes DT, not DT_; path 0), with fewer the result is identity (path 3).  Not good: gaussNewtonOptimizationRobust
+ *   from the start pose for max_iters_ref (:386, :460-507; path 1): r unscaled, w = cauchy(r / s) with s_p, s_l = vector_stdv_mad of
+ *   the inlier residuals of each kind at the pass's pose clamped to [1e-4, sqrt(7.815)], the overlap weight still applied, exit tests
+ *   before the solve, |x| < min_error_change after it; logAbsDeterminant() < 0 restores the pose, err = -1 and DT_cov = I;
+ *   the cut (removeOutliers, :1015-1094; vector_mean_stdv_mad, stvo-pl/src/auxiliar.cpp:387-430), per kind, a kind without a feature
+ *   skipped: the residuals |err| sqrt(sigma2) of ALL features of the kind enter the statistics, flagged or not; median = element n / 2
+ *   of the sorted list; the deviations pass through fabsf, i.e. are rounded to float; stdv = 1.4826 x element n / 2 of the sorted
+ *   deviations; the mean runs over r < 2 stdv unless fewer than int(0.2 n) qualify, then over all; a FLAGGED feature is removed when
+ *   |r - mean| > inlier_k stdv;
+ *   the end (:399-418): good = isGoodSolution && DT != I; then DT16 = expmap(logmap(inverse(DT))), else identity, err = -1, cov_eig6 = 0.
+ * Input, CSR over the problems as in plba_relative_pose.  Per point: P3 in the previous frame, uv2 = pl_obs in the current one,
+ * pt_sigma2.  Per line: sPeP6 in the previous frame, l3 = le_obs, spl_epl4 = the observed end points lineSegmentOverlap takes,
+ * ln_sigma2.  T0_16 (optional): B row-major 4 x 4 start poses DT; NULL = identity.  The motion-model decision of :344-353 is the
+ * caller's (include/plba_g2o/track_pose.h makes it).  pt_inlier / ln_inlier: in/out masks as in plba_relative_pose, NULL = all.
+ * Composing Tfw and Tfw_cov (:404-405) stays with the caller.  No limit on a problem's feature count beyond int32.
+ * Deviations: a non-finite e ends the run: PLBA_TRACK_NONFINITE, not good.  A final H that is rank deficient by the
+ * QR's rule, where the text inverts regardless: PLBA_TRACK_RANK, not good, cov36 = 0; a first stage with such an H is not good and
+ * takes the fallback.  cov_eig6 are the reciprocals of the eigenvalues of H (fixed-sweep Jacobi), where the reference decomposes
+ * H.inverse().  A stage whose iteration limit is 0 evaluates no pass and reports H = 0, e = 0 (the reference: uninitialised), hence
+ * RANK.  DT_cov left stale by the err = -1 return of :435 is never used (err < 0 fails the test) and is not reproduced.
+ * Refused with PLBA_ERR_INVALID and every output untouched: the refusals of plba_relative_pose, a negative min_features, a negative or
+ * non-finite sigma2, a non-finite option.  `p` supplies the device, the stream and the error text; the uploaded window, prior, trace
+ * and saved state are neither read nor written.  One staged copy up, one back, one blocking wait (plba_debug_get("host_waits")).  A
+ * problem's result does not depend on B or on its neighbours; two calls give the same bits. */
+#define PLBA_TRACK_OK 0
+#define PLBA_TRACK_NONFINITE 2    /* a pass gave a non-finite e                                   */
+#define PLBA_TRACK_RANK 3         /* the final H is rank deficient: no covariance                 */
+typedef struct plba_track_options {
+    int    max_iters;         /* Config::maxIters        first-stage iterations           (5)     */
+    int    max_iters_ref;     /* Config::maxItersRef     refinement / fallback iterations (10)    */
+    int    min_features;      /* Config::minFeatures                                      (10)    */
+    int    reserved;
+    double homog_th;          /* Config::homogTh         floor of gz^2 and of the norm    (1e-7)  */
+    double min_error;         /* Config::minError                                         (1e-7)  */
+    double min_error_change;  /* Config::minErrorChange                                   (1e-7)  */
+    double inlier_k;          /* Config::inlierK         the cut is inlier_k x 1.4826 MAD (4.0)   */
+} plba_track_options;
+typedef struct plba_track_result {
+    double  DT16[16];         /* what curr_frame->DT becomes (:401), identity when not good (:412) */
+    double  T_opt16[16];      /* DT as the optimiser left it                                     */
+    double  H36[36];          /* of the last pass evaluated; row-major, symmetric                */
+    double  cov36[36];        /* DT_cov as the optimiser left it: H^-1, I after :504, else 0     */
+    double  cov_eig6[6];      /* ascending; zeros when not good (:417)                           */
+    double  err;              /* -1 when not good                                                */
+    double  pt_mean, pt_stdv, ln_mean, ln_stdv;   /* the cut's statistics; 0 when it did not run */
+    int32_t n_inliers_pt, n_inliers_ln;
+    int32_t iters[3];         /* passes of the first stage, the refinement, the robust fallback  */
+    int32_t path;             /* 0 refined, 1 robust fallback, 2 too few before, 3 after the cut */
+    int32_t status;           /* PLBA_TRACK_*                                                    */
+    int32_t good;             /* isGoodSolution && DT != I of :399                               */
+} plba_track_result;
+void plba_track_default_options(plba_track_options* o);
+int  plba_track_pose(plba_problem* p, const plba_track_options* opt, int B,
+                     const int32_t* pt_start, const double* P3, const double* uv2, const double* pt_sigma2,
+                     const int32_t* ln_start, const double* sPeP6, const double* l3, const double* spl_epl4, const double* ln_sigma2,
+                     double fx, double fy, double cx, double cy, const double* T0_16,
+                     uint8_t* pt_inlier, uint8_t* ln_inlier, plba_track_result* out);
+
 /* ---- diagnostics used by the parity tests (not needed by a drop-in caller) ------------------- */
 /* Runs computeActiveErrors + buildSystem + setLambda(lambda) + Schur on the current state without
  * updating it, then exposes named internal buffers: "Hschur" (P*P row-major), "bschur" (P),

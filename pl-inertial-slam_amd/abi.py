@@ -108,7 +108,22 @@ class RelposeResult(C.Structure):
                 ("lc_res", C.c_int32), ("lc_unc", C.c_int32), ("lc_inl", C.c_int32), ("lc_trs", C.c_int32), ("lc_rot", C.c_int32)]
 
 
+class TrackOptions(C.Structure):
+    """plba_track_options of include/plba.h"""
+    _fields_ = [("max_iters", C.c_int), ("max_iters_ref", C.c_int), ("min_features", C.c_int), ("reserved", C.c_int), ("homog_th", C.c_double),
+                ("min_error", C.c_double), ("min_error_change", C.c_double), ("inlier_k", C.c_double)]
+
+
+class TrackResult(C.Structure):
+    """plba_track_result of include/plba.h"""
+    _fields_ = [("DT16", C.c_double * 16), ("T_opt16", C.c_double * 16), ("H36", C.c_double * 36), ("cov36", C.c_double * 36), ("cov_eig6", C.c_double * 6),
+                ("err", C.c_double), ("pt_mean", C.c_double), ("pt_stdv", C.c_double), ("ln_mean", C.c_double), ("ln_stdv", C.c_double),
+                ("n_inliers_pt", C.c_int32), ("n_inliers_ln", C.c_int32), ("iters", C.c_int32 * 3), ("path", C.c_int32), ("status", C.c_int32), ("good", C.c_int32)]
+
+
 RELPOSE_OK, RELPOSE_EMPTY, RELPOSE_NONFINITE, RELPOSE_RANK = range(4)
+TRACK_OK, TRACK_NONFINITE, TRACK_RANK = 0, 2, 3
+TRACK_REFINED, TRACK_ROBUST, TRACK_FEW_BEFORE, TRACK_FEW_AFTER = range(4)
 REFINE_DONE, REFINE_EXHAUSTED, REFINE_NONFINITE, REFINE_FIXED, REFINE_UNSELECTED, REFINE_NO_OBS = range(6)
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
@@ -119,9 +134,10 @@ _P = C.c_void_p  # plba_problem*
 # CPU oracle — a restatement of the reference — does not implement them
 # (compute_marginals: the reference computes no marginals; the oracle has no such entry.  optimize_pose_graph: the oracle restates the
 # pose graph as orc_pgo, a checker entry of its own outside this table.  refine_landmarks: g2o's structure-only solver is a stub at the
-# reference's boundary; its checker is the numpy restatement tests/refine_ref.py.  relative_pose: its checker is tests/relpose_ref.py)
+# reference's boundary; its checker is the numpy restatement tests/refine_ref.py.  relative_pose: its checker is tests/relpose_ref.py.
+# track_pose: its checker is tests/track_ref.py)
 PRODUCT_ONLY = {"slide_window", "get_sizes", "marginalize_to_prior", "get_prior", "compute_marginals", "optimize_pose_graph",
-                "refine_default_options", "refine_landmarks", "relpose_default_options", "relative_pose"}
+                "refine_default_options", "refine_landmarks", "relpose_default_options", "relative_pose", "track_default_options", "track_pose"}
 
 # name -> (restype, argtypes); every symbol plba.h declares
 SIGNATURES = {
@@ -178,6 +194,9 @@ SIGNATURES = {
     "relpose_default_options": (None, [C.POINTER(RelposeOptions)]),
     "relative_pose": (C.c_int, [_P, C.POINTER(RelposeOptions), C.c_int, c_int32_p, c_double_p, c_double_p, c_int32_p, c_double_p, c_double_p,
                                 C.c_double, C.c_double, C.c_double, C.c_double, c_double_p, c_uint8_p, c_uint8_p, C.POINTER(RelposeResult)]),
+    "track_default_options": (None, [C.POINTER(TrackOptions)]),
+    "track_pose": (C.c_int, [_P, C.POINTER(TrackOptions), C.c_int, c_int32_p, c_double_p, c_double_p, c_double_p, c_int32_p, c_double_p, c_double_p,
+                             c_double_p, c_double_p, C.c_double, C.c_double, C.c_double, C.c_double, c_double_p, c_uint8_p, c_uint8_p, C.POINTER(TrackResult)]),
     "optimize_pose_graph": (C.c_int, [_P, C.POINTER(PoseGraph), C.c_int, C.c_double, C.c_int, C.POINTER(Stats), C.POINTER(TraceRow), C.c_int, C.POINTER(C.c_int)]),
 }
 
@@ -700,6 +719,59 @@ class Problem:
         for k in ("e", "t", "r"):
             out[k] = np.array([getattr(r, k) for r in res[:B]], np.float64)
         for k in ("n_inliers", "status", "accepted", "lc_res", "lc_unc", "lc_inl", "lc_trs", "lc_rot"):
+            out[k] = np.array([getattr(r, k) for r in res[:B]], np.int32)
+        out["pt_inlier"] = [pm[ps[b]:ps[b + 1]].astype(bool) for b in range(B)]
+        out["ln_inlier"] = [lm[ls[b]:ls[b + 1]].astype(bool) for b in range(B)]
+        return out
+
+    def track_pose(self, P3, uv, pt_sigma2, sPeP, l3, spl_epl, ln_sigma2, cam, T0=None, pt_inlier=None, ln_inlier=None, **opts):
+        """plba_track_pose: B frame-to-frame pose estimates (StereoFrameHandler::optimizePose) in one launch.  P3 / uv / pt_sigma2 / sPeP / l3 /
+        spl_epl / ln_sigma2: lists of B arrays ((n, 3), (n, 2), (n,), (m, 6), (m, 3), (m, 4), (m,); an empty array or None for a problem without
+        points or lines); cam = (fx, fy, cx, cy); T0: (B, 4, 4) start poses or None (identity); pt_inlier / ln_inlier: lists of B masks or None
+        (all); opts: the fields of plba_track_options.  Returns a dict of arrays over the problems — DT, T_opt (B, 4, 4), H, cov (B, 6, 6),
+        cov_eig (B, 6), err, pt_mean, pt_stdv, ln_mean, ln_stdv, n_inliers_pt, n_inliers_ln, iters (B, 3), path, status, good — and
+        pt_inlier / ln_inlier, lists of B boolean masks as the cut left them."""
+        o = TrackOptions()
+        self.lib.fn["track_default_options"](C.byref(o))
+        for k, v in opts.items():
+            if k == "reserved" or not hasattr(o, k):
+                raise TypeError("unknown track-pose option %r" % k)
+            setattr(o, k, v)
+        B = len(P3)
+        if not (len(uv) == len(pt_sigma2) == len(sPeP) == len(l3) == len(spl_epl) == len(ln_sigma2) == B):
+            raise ValueError("the feature lists must list the same problems")
+
+        def csr(lists, width):
+            arrs = [np.zeros((0, width)) if a is None else _f64(a).reshape(-1, width) for a in lists]
+            start = np.zeros(len(arrs) + 1, np.int32)
+            start[1:] = np.cumsum([len(a) for a in arrs])
+            return start, (np.concatenate(arrs) if arrs else np.zeros((0, width)))
+        ps, P = csr(P3, 3); ps2, U2 = csr(uv, 2); ps3, S2P = csr(pt_sigma2, 1)
+        ls, PQ = csr(sPeP, 6); ls2, L3 = csr(l3, 3); ls3, SE = csr(spl_epl, 4); ls4, S2L = csr(ln_sigma2, 1)
+        if not (np.array_equal(ps, ps2) and np.array_equal(ps, ps3) and np.array_equal(ls, ls2) and np.array_equal(ls, ls3) and np.array_equal(ls, ls4)):
+            raise ValueError("a problem's point arrays or line arrays differ in length")
+
+        def masks(m, start):
+            if m is None:
+                return np.ones(max(int(start[-1]), 1), np.uint8)
+            if len(m) != B or any(len(np.asarray(a).ravel()) != start[b + 1] - start[b] for b, a in enumerate(m)):
+                raise ValueError("a mask list must have one entry per problem and one flag per feature")
+            flat = np.concatenate([np.asarray(a).ravel().astype(bool) for a in m]) if B else np.zeros(0, bool)
+            return np.concatenate([flat.astype(np.uint8), np.zeros(1 if flat.size == 0 else 0, np.uint8)])
+        pm, lm = masks(pt_inlier, ps), masks(ln_inlier, ls)
+        T = None if T0 is None else _f64(T0).reshape(-1, 16).copy()
+        if T is not None and T.shape[0] != B:
+            raise ValueError("T0 must be (B, 4, 4)")
+        res = (TrackResult * max(B, 1))()
+        opt_p = lambda a: _dp(a) if len(a) else None
+        self.call("track_pose", C.byref(o), B, _ip(ps), opt_p(P), opt_p(U2), opt_p(S2P), _ip(ls), opt_p(PQ), opt_p(L3), opt_p(SE), opt_p(S2L),
+                  float(cam[0]), float(cam[1]), float(cam[2]), float(cam[3]), _dp(T), _up(pm), _up(lm), res)
+        arr = lambda f, shape: np.array([list(getattr(r, f)) for r in res[:B]], np.float64).reshape((B,) + shape)
+        out = dict(DT=arr("DT16", (4, 4)), T_opt=arr("T_opt16", (4, 4)), H=arr("H36", (6, 6)), cov=arr("cov36", (6, 6)), cov_eig=arr("cov_eig6", (6,)),
+                   iters=np.array([list(r.iters) for r in res[:B]], np.int32).reshape(B, 3))
+        for k in ("err", "pt_mean", "pt_stdv", "ln_mean", "ln_stdv"):
+            out[k] = np.array([getattr(r, k) for r in res[:B]], np.float64)
+        for k in ("n_inliers_pt", "n_inliers_ln", "path", "status", "good"):
             out[k] = np.array([getattr(r, k) for r in res[:B]], np.int32)
         out["pt_inlier"] = [pm[ps[b]:ps[b + 1]].astype(bool) for b in range(B)]
         out["ln_inlier"] = [lm[ls[b]:ls[b + 1]].astype(bool) for b in range(B)]

@@ -202,7 +202,8 @@ RP_HD void tree_sum(Acc* lanes, int nl) {
 // ---- the 6 x 6 solve: Eigen's ColPivHouseholderQR by its documented algorithm ------------------------------------
 // Householder QR with column pivoting by the largest remaining column norm (the first of equals), rank = the pivots above
 // eps 6 |largest pivot|, the deficient part of the solution zero.  H21: upper entries row by row.  Returns the rank; x may be null.
-RP_HD int qr_solve6(const double* H21, const double* g, double* x) {
+// piv_out (optional): the six |R_kk| in pivot order, for logAbsDeterminant (plba_track_dev.h).
+RP_HD int qr_solve6(const double* H21, const double* g, double* x, double* piv_out = nullptr) {
     double A[6][6], c[6], piv[6];
     int perm[6];
     {
@@ -247,6 +248,7 @@ RP_HD int qr_solve6(const double* H21, const double* g, double* x) {
     }
     double big = 0.0;
     for (int k = 0; k < 6; ++k) big = piv[k] > big ? piv[k] : big;
+    if (piv_out) for (int k = 0; k < 6; ++k) piv_out[k] = piv[k];
     const double thr = EPS * 6.0 * big;
     int rank = 0;
     for (int k = 0; k < 6; ++k) rank += piv[k] > thr ? 1 : 0;
@@ -346,7 +348,7 @@ struct Thresholds { double lc_res, lc_unc, lc_inl, lc_trs, lc_rot; };
 struct Decision { double cov_eig[6], t, r; int status, lc_res, lc_unc, lc_inl, lc_trs, lc_rot, accepted; };
 
 // eigenvalues of a symmetric 6 x 6 (upper entries row by row) by cyclic Jacobi, a fixed number of sweeps; ascending
-inline void sym_eig6(const double* H21, double* ev) {
+RP_HD void sym_eig6(const double* H21, double* ev) {
     double A[6][6];
     int q = 0;
     for (int i = 0; i < 6; ++i)

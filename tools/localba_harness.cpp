@@ -15,6 +15,9 @@
 //   localba_harness lba     <in.bin> <out.bin>          MapHandler::localBundleAdjustment + levMarquardtOptimizationLBA (:1329-2098): the
 //                                                       pre-init visual-only path, which does not use g2o at all: its list building on
 //                                                       map-shaped objects, then the optimiser's body as one plba_lba_visual call
+//   localba_harness track   <in.bin> <out.bin>          MapHandler::lookForCommonMatches' pose refinement (:819-859) for B keyframe pairs:
+//                                                       the matched lists, StereoFrameHandler::optimizePose as one plba_track_pose call,
+//                                                       the inlier ratios and kf1->T_kf_w
 #include "plba_g2o/vio_init.h"
 #include <cstdint>
 #include <cstdio>
@@ -295,6 +298,7 @@ static int vio_init(const char* in, const char* out) {
 }
 
 static int relpose(const char* in, const char* out);
+static int track(const char* in, const char* out);
 int main(int argc, char** argv) {
     if (argc >= 4 && !strcmp(argv[1], "gyrbias")) return imu_init_est_bg(argv[2], argv[3]);
     if (argc >= 4 && !strcmp(argv[1], "pgo")) return pose_graph(argv[2], argv[3]);
@@ -309,6 +313,7 @@ int main(int argc, char** argv) {
     if (argc >= 4 && !strcmp(argv[1], "scrambled")) { g_scrambled = true; return local_ba_with_imu_and_marg(argv[2], argv[3], nullptr); }
     if (argc >= 4 && !strcmp(argv[1], "lba")) return visual_lba(argv[2], argv[3]);
     if (argc >= 4 && !strcmp(argv[1], "relpose")) return relpose(argv[2], argv[3]);
+    if (argc >= 4 && !strcmp(argv[1], "track")) return track(argv[2], argv[3]);
     if (argc >= 4 && !strcmp(argv[1], "structonly")) return structure_only(argv[2], argv[3], false);
     if (argc >= 4 && !strcmp(argv[1], "structonly_bad")) return structure_only(argv[2], argv[3], true);
     // `time window.bin reps`: one localBundleAdjustmentWithImuAndMarg-shaped call through Boundary 1, `reps` times on fresh optimizers, lap by lap
@@ -967,5 +972,103 @@ static int relpose(const char* in, const char* out) {
     wr(o, od); wr(o, oi); wr(o, pmo); wr(o, lmo);
     fclose(o);
     printf("relpose: %d of %d candidates are loop closures\n", n_loops, B);
+    return 0;
+}
+
+// MapHandler::lookForCommonMatches' pose refinement between two keyframes (src/mapHandler.cpp:819-859) for B keyframe pairs at once: from
+// the matched lists (stf->matched_pt, stf->matched_ls with every feature an inlier unless the file says otherwise, :821-829) to the arrays
+// of plba_track_pose, through the call (stf->optimizePose(), :831), to the inlier ratios against SlamConfig::kfInlierRatio() (30, :833-846)
+// and kf1->T_kf_w (:848-852).  kf0->T_kf_w is the identity here and the tracker's DT of :852 is the start pose of the file.  A kind
+// without a match counts as absent (SlamConfig::hasPoints() / hasLines()): the reference would divide by its zero count.  Input: the file
+// of csrc/plba_track_hostcheck.cpp.  Output: that program's, then per pair double T_kf_w[16] and int32 [used the refined DT].
+#include "plba_g2o/track_pose.h"
+static int track(const char* in, const char* out) {
+    namespace rp = plba::relpose;
+    FILE* f = fopen(in, "rb");
+    if (!f) { perror("batch"); return 2; }
+    auto hd = rd<int32_t>(f, 6); auto par = rd<double>(f, 8);
+    const int B = hd[0];
+    auto ps = rd<int32_t>(f, (size_t)B + 1), ls = rd<int32_t>(f, (size_t)B + 1);
+    const size_t Np = (size_t)ps[B], Nl = (size_t)ls[B];
+    auto P = rd<double>(f, 3 * Np), uv = rd<double>(f, 2 * Np), s2p = rd<double>(f, Np), pq = rd<double>(f, 6 * Nl), l3 = rd<double>(f, 3 * Nl), se = rd<double>(f, 4 * Nl),
+         s2l = rd<double>(f, Nl);
+    std::vector<double> T0; if (hd[4]) T0 = rd<double>(f, 16 * (size_t)B);
+    std::vector<uint8_t> pm(Np, 1), lm(Nl, 1);
+    if (hd[5]) { pm = rd<uint8_t>(f, Np); lm = rd<uint8_t>(f, Nl); }
+    fclose(f);
+    // the matched lists of every pair
+    std::vector<std::vector<plba_g2o::TrackPoint>> matched_pt(B);
+    std::vector<std::vector<plba_g2o::TrackLine>> matched_ls(B);
+    for (int b = 0; b < B; ++b) {
+        for (int k = ps[b]; k < ps[b + 1]; ++k) {
+            plba_g2o::TrackPoint pt; std::memcpy(pt.P, &P[3 * (size_t)k], 24); std::memcpy(pt.pl_obs, &uv[2 * (size_t)k], 16); pt.sigma2 = s2p[k]; pt.inlier = pm[k] != 0;
+            matched_pt[b].push_back(pt);
+        }
+        for (int k = ls[b]; k < ls[b + 1]; ++k) {
+            plba_g2o::TrackLine ln; std::memcpy(ln.sP, &pq[6 * (size_t)k], 24); std::memcpy(ln.eP, &pq[6 * (size_t)k + 3], 24); std::memcpy(ln.le_obs, &l3[3 * (size_t)k], 24);
+            std::memcpy(ln.spl, &se[4 * (size_t)k], 16); std::memcpy(ln.epl, &se[4 * (size_t)k + 2], 16); ln.sigma2 = s2l[k]; ln.inlier = lm[k] != 0;
+            matched_ls[b].push_back(ln);
+        }
+    }
+    // lists -> arrays
+    std::vector<int32_t> pt_start(B + 1, 0), ln_start(B + 1, 0);
+    std::vector<double> aP, auv, as2p, apq, al3, ase, as2l;
+    std::vector<uint8_t> apm, alm;
+    for (int b = 0; b < B; ++b) {
+        for (const auto& pt : matched_pt[b]) { aP.insert(aP.end(), pt.P, pt.P + 3); auv.insert(auv.end(), pt.pl_obs, pt.pl_obs + 2); as2p.push_back(pt.sigma2); apm.push_back(pt.inlier ? 1 : 0); }
+        for (const auto& ln : matched_ls[b]) {
+            apq.insert(apq.end(), ln.sP, ln.sP + 3); apq.insert(apq.end(), ln.eP, ln.eP + 3); al3.insert(al3.end(), ln.le_obs, ln.le_obs + 3);
+            ase.insert(ase.end(), ln.spl, ln.spl + 2); ase.insert(ase.end(), ln.epl, ln.epl + 2); as2l.push_back(ln.sigma2); alm.push_back(ln.inlier ? 1 : 0);
+        }
+        pt_start[b + 1] = (int32_t)apm.size(); ln_start[b + 1] = (int32_t)alm.size();
+    }
+    apm.push_back(0); alm.push_back(0);
+    plba_problem* p = nullptr;
+    if (plba_create(nullptr, &p) != PLBA_OK) { fprintf(stderr, "track: %s\n", plba_last_error(nullptr)); return 2; }
+    plba_track_options to; plba_track_default_options(&to);
+    to.max_iters = hd[1]; to.max_iters_ref = hd[2]; to.min_features = hd[3]; to.homog_th = par[0]; to.min_error = par[1]; to.min_error_change = par[2]; to.inlier_k = par[3];
+    std::vector<plba_track_result> res(B);
+    auto ptr = [](std::vector<double>& v) { return v.empty() ? nullptr : v.data(); };
+    const int rc = plba_track_pose(p, &to, B, pt_start.data(), ptr(aP), ptr(auv), ptr(as2p), ln_start.data(), ptr(apq), ptr(al3), ptr(ase), ptr(as2l),
+                                   par[4], par[5], par[6], par[7], hd[4] ? T0.data() : nullptr, apm.data(), alm.data(), res.data());
+    if (rc != PLBA_OK) { fprintf(stderr, "track: %s\n", plba_last_error(p)); plba_destroy(p); return 2; }
+    plba_destroy(p);
+    std::vector<double> od((size_t)B * 115, 0.0), Tkf((size_t)B * 16, 0.0);
+    std::vector<int32_t> oi((size_t)B * 8, 0), used(B, 0);
+    std::vector<uint8_t> pmo(Np, 0), lmo(Nl, 0);
+    const double kf_inlier_ratio = 30.0;      // SlamConfig::kfInlierRatio(), src/slamConfig.cpp:57
+    int n_used = 0;
+    for (int b = 0; b < B; ++b) {
+        const plba_track_result& r = res[b];
+        for (size_t i = 0; i < matched_pt[b].size(); ++i) { matched_pt[b][i].inlier = apm[(size_t)pt_start[b] + i] != 0; pmo[(size_t)ps[b] + i] = apm[(size_t)pt_start[b] + i]; }
+        for (size_t i = 0; i < matched_ls[b].size(); ++i) { matched_ls[b][i].inlier = alm[(size_t)ln_start[b] + i] != 0; lmo[(size_t)ls[b] + i] = alm[(size_t)ln_start[b] + i]; }
+        const bool has_pt = !matched_pt[b].empty(), has_ls = !matched_ls[b].empty();
+        bool condition_pt = true, condition_ls = true;
+        if (has_pt) condition_pt = 100.0 * r.n_inliers_pt / (double)matched_pt[b].size() >= kf_inlier_ratio;
+        if (has_ls) condition_ls = 100.0 * r.n_inliers_ln / (double)matched_ls[b].size() >= kf_inlier_ratio;
+        if (!has_pt && !has_ls) condition_pt = condition_ls = false;
+        const bool use = r.n_inliers_pt + r.n_inliers_ln > to.min_features && condition_pt && condition_ls;      // :848
+        rp::Pose D, A, E;
+        double x[6];
+        const double* m = use ? r.DT16 : (hd[4] ? &T0[16 * (size_t)b] : nullptr);
+        if (m) { for (int i = 0; i < 3; ++i) { D.R[i * 3] = m[i * 4]; D.R[i * 3 + 1] = m[i * 4 + 1]; D.R[i * 3 + 2] = m[i * 4 + 2]; D.t[i] = m[i * 4 + 3]; } }
+        else rp::se3_identity(D);
+        if (use) A = D; else rp::se3_inv(D, A);      // :850 / :852 with kf0->T_kf_w = I
+        rp::se3_log(A, x); rp::se3_exp(x, E);
+        double* t = &Tkf[(size_t)b * 16];
+        for (int i = 0; i < 3; ++i) { t[i * 4] = E.R[i * 3]; t[i * 4 + 1] = E.R[i * 3 + 1]; t[i * 4 + 2] = E.R[i * 3 + 2]; t[i * 4 + 3] = E.t[i]; }
+        t[15] = 1.0;
+        used[b] = use ? 1 : 0; n_used += used[b];
+        double* o = &od[(size_t)b * 115];
+        std::memcpy(o, r.DT16, 128); std::memcpy(o + 16, r.T_opt16, 128); std::memcpy(o + 32, r.H36, 288); std::memcpy(o + 68, r.cov36, 288); std::memcpy(o + 104, r.cov_eig6, 48);
+        o[110] = r.err; o[111] = r.pt_mean; o[112] = r.pt_stdv; o[113] = r.ln_mean; o[114] = r.ln_stdv;
+        int32_t* q = &oi[(size_t)b * 8];
+        q[0] = r.n_inliers_pt; q[1] = r.n_inliers_ln; q[2] = r.iters[0]; q[3] = r.iters[1]; q[4] = r.iters[2]; q[5] = r.path; q[6] = r.status; q[7] = r.good;
+    }
+    FILE* o = fopen(out, "wb");
+    if (!o) { perror("result"); return 2; }
+    wr(o, od); wr(o, oi); wr(o, pmo); wr(o, lmo); wr(o, Tkf); wr(o, used);
+    fclose(o);
+    printf("track: %d of %d keyframe pairs take the refined pose\n", n_used, B);
     return 0;
 }
