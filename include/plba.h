@@ -651,6 +651,75 @@ int  plba_track_pose(plba_problem* p, const plba_track_options* opt, int B,
                      double fx, double fy, double cx, double cy, const double* T0_16,
                      uint8_t* pt_inlier, uint8_t* ln_inlier, plba_track_result* out);
 
+/* ---- descriptor matching and loop-candidate checks: batched StVO::match and isLoopClosure -------------
+ * plba_match_descriptors: StVO::match (stvo-pl/src/matching.cpp:41-91) for B problems in ONE launch over (problem, direction, query
+ * tile), a second small launch for the tests and the counts.  Semantics, literally as coded there:
+ *   the distance is the Hamming distance over 8 x 32-bit words (:93-109);
+ *   per query row, the two smallest distances over all train rows, visited in ascending train index; a tied distance keeps the LOWER
+ *   train index first.  That is OpenCV's brute-force k-NN insertion as far as it is remembered; OpenCV is not available to this project,
+ *   so the rule is UNPINNED.  For nnr <= 1 a tied best can never pass the test (d0 < d0 nnr is false): the rule shows
+ *   only in nn3 and for nnr > 1;
+ *   the ratio test is made in float: (float)d0 < (float)d1 * nnr, one rounding of the product (:54; nnr = 0.8f, (d0, d1) = (4, 5)
+ *   passes in double and fails in float);
+ *   with best_lr the same search runs with the roles swapped and i1 -> i2 is cleared unless matches_21[i2] == i1; n_matches is the
+ *   count after clearing (:80-86).
+ * Input, CSR over the problems: problem b owns the rows [a_start[b], a_start[b+1]) of descA32 (desc1, 32 bytes a row) and
+ * [b_start[b], b_start[b+1]) of descB32 (desc2).  nnr_b (optional): one ratio per problem, NULL = opt->nnr for all.  matches_12
+ * (a_start[B]): per row of desc1 the index INTO THE PROBLEM'S OWN desc2 rows, or -1.  n_matches (B).  nn3 (optional, a_start[B] x 3):
+ * best index, d0, d1 of the search 1 -> 2, -1 where the train set has no such row.
+ * Deviations: a direction whose train set has fewer than two rows yields no match (the reference reads matches_[idx][1] out of bounds
+ * there); an empty side gives all -1 and a count of 0 (the reference's callers guard that).
+ * Refused with PLBA_ERR_INVALID and every output untouched: B < 1, starts that do not begin at 0 or descend, a missing array whose count
+ * is non-zero, a missing output or options, nnr (or an nnr_b) not finite or <= 0.  `p` supplies the device, the stream and the error
+ * text; the uploaded window, prior, trace and saved state are neither read nor written.  One staged copy up, one back, one blocking wait
+ * (plba_debug_get("host_waits")).  A problem's result does not depend on B or on its neighbours; two calls give the same bits.  No size
+ * limit beyond int32 row counts. */
+typedef struct plba_match_options {
+    float nnr;       /* Config::minRatio12P / minRatio12L (0.9f): the test is (float)d0 < (float)d1 * nnr, in float */
+    int   best_lr;   /* Config::bestLRMatches (1): keep i1 -> i2 only when the search 2 -> 1 gives i2 -> i1 */
+} plba_match_options;
+void plba_match_default_options(plba_match_options* o);
+int  plba_match_descriptors(plba_problem* p, const plba_match_options* opt, int B,
+                            const int32_t* a_start, const uint8_t* descA32, const int32_t* b_start, const uint8_t* descB32,
+                            const float* nnr_b, int32_t* matches_12, int32_t* n_matches, int32_t* nn3);
+
+/* plba_verify_loop_candidates: MapHandler::isLoopClosure (src/mapHandler.cpp:3301-3409) for B candidates (kf0, kf1) with one upload, one
+ * read-back and one blocking wait.  Per candidate, as :3325-3407: match the point descriptors and the line descriptors (a kind is
+ * skipped when its use_* flag is 0 or a side is empty); inl_ratio = max(100.0 * common / n0, 100.0 * common / n1) in double, max being
+ * std::max, (a < b) ? b : a: n0 = 0 gives NaN, n1 = 0 alone gives 0; the gate is the strict inl_ratio > lc_inlier_ratio, for both kinds
+ * when both are in use, otherwise for the one in use; the matched pairs are gathered in ascending i1 (points: P3A[i1], uvB[i2]; lines:
+ * sPeP6A[i1], l3B[i2]) and handed to plba_relative_pose's kernel, a candidate that fails the gate with no features; its relpose is
+ * then reported all zero and ratio_ok = 0 (the reference returns false without estimating).  Counts, the scan over B, the gather and
+ * the estimate all run on the device; the decision code of plba_relative_pose runs on the host after the read-back.
+ * The results (relpose, pt_match, ln_match, the masks, the counts) are bit-identical to two plba_match_descriptors calls, the gate and
+ * the gather on the host and one plba_relative_pose call on the same data.
+ * Input, CSR over the candidates, one pair of starts per array pair: pa_start: kf0's stereo points (descPA32, P3A = stereo_pt[i]->P);
+ * pb_start: kf1's (descPB32, uvB = stereo_pt[i]->pl); la_start: kf0's line segments (descLA32, sPeP6A = sP, eP); lb_start: kf1's
+ * (descLB32, l3B = le).  pt_match (pa_start[B]) / ln_match (la_start[B]): matches_12, i.e. lc_pt_idx(1) -> (3), whether or not the gate
+ * passed.  pt_inlier / ln_inlier (optional, out only, same lengths): 1 where the matched pair survived the estimate's cut.
+ * Refused with PLBA_ERR_INVALID and every output untouched: the refusals of plba_match_descriptors and of plba_relative_pose, a
+ * non-finite lc_inlier_ratio, more than 2^31 - 1 rows on a side in all.  The contract of plba_match_descriptors otherwise. */
+typedef struct plba_loop_options {
+    plba_match_options   match_pt, match_ln;   /* minRatio12P / minRatio12L */
+    int                  use_points, use_lines;/* SlamConfig::hasPoints / hasLines (1, 1) */
+    double               lc_inlier_ratio;      /* SlamConfig::lcInlierRatio, percent (30.0) */
+    plba_relpose_options relpose;
+} plba_loop_options;
+typedef struct plba_loop_result {
+    int32_t common_pt, common_ls;              /* match()'s counts (:3332, :3358) */
+    int32_t ratio_ok, reserved;                /* the gate of :3382-3400 */
+    double  inl_ratio_pt, inl_ratio_ls;
+    plba_relpose_result relpose;               /* all zero when ratio_ok = 0 (the reference returns false without estimating) */
+} plba_loop_result;
+void plba_loop_default_options(plba_loop_options* o);
+int  plba_verify_loop_candidates(plba_problem* p, const plba_loop_options* opt, int B,
+        const int32_t* pa_start, const uint8_t* descPA32, const double* P3A,
+        const int32_t* pb_start, const uint8_t* descPB32, const double* uvB,
+        const int32_t* la_start, const uint8_t* descLA32, const double* sPeP6A,
+        const int32_t* lb_start, const uint8_t* descLB32, const double* l3B,
+        double fx, double fy, double cx, double cy,
+        int32_t* pt_match, int32_t* ln_match, uint8_t* pt_inlier, uint8_t* ln_inlier, plba_loop_result* out);
+
 /* ---- diagnostics used by the parity tests (not needed by a drop-in caller) ------------------- */
 /* Runs computeActiveErrors + buildSystem + setLambda(lambda) + Schur on the current state without
  * updating it, then exposes named internal buffers: "Hschur" (P*P row-major), "bschur" (P),

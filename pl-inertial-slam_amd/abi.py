@@ -121,6 +121,23 @@ class TrackResult(C.Structure):
                 ("n_inliers_pt", C.c_int32), ("n_inliers_ln", C.c_int32), ("iters", C.c_int32 * 3), ("path", C.c_int32), ("status", C.c_int32), ("good", C.c_int32)]
 
 
+class MatchOptions(C.Structure):
+    """plba_match_options of include/plba.h"""
+    _fields_ = [("nnr", C.c_float), ("best_lr", C.c_int)]
+
+
+class LoopOptions(C.Structure):
+    """plba_loop_options of include/plba.h"""
+    _fields_ = [("match_pt", MatchOptions), ("match_ln", MatchOptions), ("use_points", C.c_int), ("use_lines", C.c_int), ("lc_inlier_ratio", C.c_double),
+                ("relpose", RelposeOptions)]
+
+
+class LoopResult(C.Structure):
+    """plba_loop_result of include/plba.h"""
+    _fields_ = [("common_pt", C.c_int32), ("common_ls", C.c_int32), ("ratio_ok", C.c_int32), ("reserved", C.c_int32), ("inl_ratio_pt", C.c_double),
+                ("inl_ratio_ls", C.c_double), ("relpose", RelposeResult)]
+
+
 RELPOSE_OK, RELPOSE_EMPTY, RELPOSE_NONFINITE, RELPOSE_RANK = range(4)
 TRACK_OK, TRACK_NONFINITE, TRACK_RANK = 0, 2, 3
 TRACK_REFINED, TRACK_ROBUST, TRACK_FEW_BEFORE, TRACK_FEW_AFTER = range(4)
@@ -135,9 +152,10 @@ _P = C.c_void_p  # plba_problem*
 # (compute_marginals: the reference computes no marginals; the oracle has no such entry.  optimize_pose_graph: the oracle restates the
 # pose graph as orc_pgo, a checker entry of its own outside this table.  refine_landmarks: g2o's structure-only solver is a stub at the
 # reference's boundary; its checker is the numpy restatement tests/refine_ref.py.  relative_pose: its checker is tests/relpose_ref.py.
-# track_pose: its checker is tests/track_ref.py)
+# track_pose: its checker is tests/track_ref.py.  match_descriptors, verify_loop_candidates: their checker is tests/match_ref.py)
 PRODUCT_ONLY = {"slide_window", "get_sizes", "marginalize_to_prior", "get_prior", "compute_marginals", "optimize_pose_graph",
-                "refine_default_options", "refine_landmarks", "relpose_default_options", "relative_pose", "track_default_options", "track_pose"}
+                "refine_default_options", "refine_landmarks", "relpose_default_options", "relative_pose", "track_default_options", "track_pose",
+                "match_default_options", "match_descriptors", "loop_default_options", "verify_loop_candidates"}
 
 # name -> (restype, argtypes); every symbol plba.h declares
 SIGNATURES = {
@@ -197,6 +215,13 @@ SIGNATURES = {
     "track_default_options": (None, [C.POINTER(TrackOptions)]),
     "track_pose": (C.c_int, [_P, C.POINTER(TrackOptions), C.c_int, c_int32_p, c_double_p, c_double_p, c_double_p, c_int32_p, c_double_p, c_double_p,
                              c_double_p, c_double_p, C.c_double, C.c_double, C.c_double, C.c_double, c_double_p, c_uint8_p, c_uint8_p, C.POINTER(TrackResult)]),
+    "match_default_options": (None, [C.POINTER(MatchOptions)]),
+    "match_descriptors": (C.c_int, [_P, C.POINTER(MatchOptions), C.c_int, c_int32_p, c_uint8_p, c_int32_p, c_uint8_p, C.POINTER(C.c_float), c_int32_p, c_int32_p,
+                                    c_int32_p]),
+    "loop_default_options": (None, [C.POINTER(LoopOptions)]),
+    "verify_loop_candidates": (C.c_int, [_P, C.POINTER(LoopOptions), C.c_int, c_int32_p, c_uint8_p, c_double_p, c_int32_p, c_uint8_p, c_double_p,
+                                         c_int32_p, c_uint8_p, c_double_p, c_int32_p, c_uint8_p, c_double_p, C.c_double, C.c_double, C.c_double, C.c_double,
+                                         c_int32_p, c_int32_p, c_uint8_p, c_uint8_p, C.POINTER(LoopResult)]),
     "optimize_pose_graph": (C.c_int, [_P, C.POINTER(PoseGraph), C.c_int, C.c_double, C.c_int, C.POINTER(Stats), C.POINTER(TraceRow), C.c_int, C.POINTER(C.c_int)]),
 }
 
@@ -232,6 +257,27 @@ def _i32(a):
 
 def _u8(a):
     return None if a is None else np.ascontiguousarray(a, dtype=np.uint8)
+
+
+def _desc_csr(lists):
+    """(start, rows) of a list of (n, 32) uint8 descriptor arrays; None or an empty array is an empty side"""
+    arrs = [np.zeros((0, 32), np.uint8) if a is None else np.ascontiguousarray(a, dtype=np.uint8).reshape(-1, 32) for a in lists]
+    start = np.zeros(len(arrs) + 1, np.int32)
+    start[1:] = np.cumsum([len(a) for a in arrs])
+    return start, (np.ascontiguousarray(np.concatenate(arrs)) if arrs else np.zeros((0, 32), np.uint8))
+
+
+def _relpose_dict(res):
+    """a list of RelposeResult as arrays over the candidates"""
+    B = len(res)
+    out = dict(T_inc=np.array([list(r.T_inc16) for r in res]).reshape(B, 4, 4), pose_inc=np.array([list(r.pose_inc6) for r in res]).reshape(B, 6),
+               H=np.array([list(r.H36) for r in res]).reshape(B, 6, 6), cov_eig=np.array([list(r.cov_eig6) for r in res]).reshape(B, 6),
+               iters=np.array([list(r.iters) for r in res], np.int32).reshape(B, 2))
+    for k in ("e", "t", "r"):
+        out[k] = np.array([getattr(r, k) for r in res], np.float64)
+    for k in ("n_inliers", "status", "accepted", "lc_res", "lc_unc", "lc_inl", "lc_trs", "lc_rot"):
+        out[k] = np.array([getattr(r, k) for r in res], np.int32)
+    return out
 
 
 class Lib:
@@ -775,6 +821,89 @@ class Problem:
             out[k] = np.array([getattr(r, k) for r in res[:B]], np.int32)
         out["pt_inlier"] = [pm[ps[b]:ps[b + 1]].astype(bool) for b in range(B)]
         out["ln_inlier"] = [lm[ls[b]:ls[b + 1]].astype(bool) for b in range(B)]
+        return out
+
+    def match_descriptors(self, desc1, desc2, nnr_b=None, want_nn3=False, **opts):
+        """plba_match_descriptors: StVO::match for B problems in one launch.  desc1 / desc2: lists of B uint8 arrays (n, 32) (an empty array
+        or None for an empty side); nnr_b: B ratios or None (opts' nnr for all); opts: the fields of plba_match_options.  Returns a dict:
+        matches_12, a list of B int32 arrays (index into the problem's desc2, or -1), n_matches (B,), and with want_nn3 nn3, a list of B
+        (n, 3) arrays (best index, d0, d1 of the search 1 -> 2)."""
+        o = MatchOptions()
+        self.lib.fn["match_default_options"](C.byref(o))
+        for k, v in opts.items():
+            if not hasattr(o, k):
+                raise TypeError("unknown match option %r" % k)
+            setattr(o, k, v)
+        B = len(desc1)
+        if len(desc2) != B:
+            raise ValueError("desc1 and desc2 must list the same problems")
+        sa, A = _desc_csr(desc1); sb, D2 = _desc_csr(desc2)
+        nb = None if nnr_b is None else np.ascontiguousarray(nnr_b, dtype=np.float32)
+        if nb is not None and nb.size != B:
+            raise ValueError("nnr_b must have one ratio per problem")
+        NA = int(sa[-1])
+        m = np.full(max(NA, 1), -2, np.int32); cnt = np.full(max(B, 1), -2, np.int32)
+        nn3 = np.full((max(NA, 1), 3), -2, np.int32) if want_nn3 else None
+        self.call("match_descriptors", C.byref(o), B, _ip(sa), _up(A) if len(A) else None, _ip(sb), _up(D2) if len(D2) else None,
+                  None if nb is None else nb.ctypes.data_as(C.POINTER(C.c_float)), _ip(m), _ip(cnt), _ip(nn3))
+        out = dict(matches_12=[m[sa[b]:sa[b + 1]].copy() for b in range(B)], n_matches=cnt[:B].copy())
+        if want_nn3:
+            out["nn3"] = [nn3[sa[b]:sa[b + 1]].copy() for b in range(B)]
+        return out
+
+    def verify_loop_candidates(self, kf0, kf1, cam, want_masks=True, **opts):
+        """plba_verify_loop_candidates: isLoopClosure for B candidates with one wait.  kf0 / kf1: lists of B dicts — kf0[b]: pdesc (n, 32),
+        P3 (n, 3), ldesc (m, 32), sPeP (m, 6); kf1[b]: pdesc, uv (n, 2), ldesc, l3 (m, 3); cam = (fx, fy, cx, cy); opts: use_points,
+        use_lines, lc_inlier_ratio, nnr_pt, nnr_ln, best_lr (both kinds) and the fields of plba_relpose_options.  Returns a dict: pt_match /
+        ln_match (lists of B int32 arrays), pt_inlier / ln_inlier (lists of B boolean masks), common_pt, common_ls, ratio_ok, inl_ratio_pt,
+        inl_ratio_ls (arrays over B) and relpose, the dict Problem.relative_pose returns without its masks."""
+        o = LoopOptions()
+        self.lib.fn["loop_default_options"](C.byref(o))
+        for k, v in opts.items():
+            if k == "nnr_pt":
+                o.match_pt.nnr = v
+            elif k == "nnr_ln":
+                o.match_ln.nnr = v
+            elif k == "best_lr":
+                o.match_pt.best_lr = o.match_ln.best_lr = int(v)
+            elif k in ("use_points", "use_lines", "lc_inlier_ratio"):
+                setattr(o, k, v)
+            elif k != "reserved" and hasattr(o.relpose, k):
+                setattr(o.relpose, k, v)
+            else:
+                raise TypeError("unknown loop option %r" % k)
+        B = len(kf0)
+        if len(kf1) != B:
+            raise ValueError("kf0 and kf1 must list the same candidates")
+
+        def csr(dicts, key, width):
+            arrs = [np.zeros((0, width)) if d.get(key) is None else _f64(d[key]).reshape(-1, width) for d in dicts]
+            start = np.zeros(len(arrs) + 1, np.int32)
+            start[1:] = np.cumsum([len(a) for a in arrs])
+            return start, (np.concatenate(arrs) if arrs else np.zeros((0, width)))
+        pa, DPA = _desc_csr([d.get("pdesc") for d in kf0]); pa2, P3 = csr(kf0, "P3", 3)
+        pb, DPB = _desc_csr([d.get("pdesc") for d in kf1]); pb2, UV = csr(kf1, "uv", 2)
+        la, DLA = _desc_csr([d.get("ldesc") for d in kf0]); la2, PQ = csr(kf0, "sPeP", 6)
+        lb, DLB = _desc_csr([d.get("ldesc") for d in kf1]); lb2, L3 = csr(kf1, "l3", 3)
+        if not (np.array_equal(pa, pa2) and np.array_equal(pb, pb2) and np.array_equal(la, la2) and np.array_equal(lb, lb2)):
+            raise ValueError("a keyframe's descriptors and features differ in length")
+        NpA, NlA = int(pa[-1]), int(la[-1])
+        pm_, lm_ = np.full(max(NpA, 1), -2, np.int32), np.full(max(NlA, 1), -2, np.int32)
+        pi, li = (np.zeros(max(NpA, 1), np.uint8), np.zeros(max(NlA, 1), np.uint8)) if want_masks else (None, None)
+        res = (LoopResult * max(B, 1))()
+        u8 = lambda a: _up(a) if len(a) else None
+        dd = lambda a: _dp(a) if len(a) else None
+        self.call("verify_loop_candidates", C.byref(o), B, _ip(pa), u8(DPA), dd(P3), _ip(pb), u8(DPB), dd(UV), _ip(la), u8(DLA), dd(PQ), _ip(lb), u8(DLB), dd(L3),
+                  float(cam[0]), float(cam[1]), float(cam[2]), float(cam[3]), _ip(pm_), _ip(lm_), _up(pi), _up(li), res)
+        out = dict(pt_match=[pm_[pa[b]:pa[b + 1]].copy() for b in range(B)], ln_match=[lm_[la[b]:la[b + 1]].copy() for b in range(B)])
+        if want_masks:
+            out["pt_inlier"] = [pi[pa[b]:pa[b + 1]].astype(bool) for b in range(B)]
+            out["ln_inlier"] = [li[la[b]:la[b + 1]].astype(bool) for b in range(B)]
+        for k in ("common_pt", "common_ls", "ratio_ok"):
+            out[k] = np.array([getattr(r, k) for r in res[:B]], np.int32)
+        for k in ("inl_ratio_pt", "inl_ratio_ls"):
+            out[k] = np.array([getattr(r, k) for r in res[:B]], np.float64)
+        out["relpose"] = _relpose_dict([r.relpose for r in res[:B]])
         return out
 
     def preintegrate(self, sample_start, t, gyr, acc, t_prev, t_curr, bg, ba, gyr_meas_cov, acc_meas_cov):

@@ -9,26 +9,16 @@
 // the other lanes by lane reads.  The cut is a lane-parallel pass over the same lane -> feature map, so a mask byte is only ever
 // touched by one lane.  A candidate is launch- and latency-bound (a handful of dependent passes over a few hundred features): the batch is
 // what fills the machine.  The arithmetic is plba_relpose_dev.h, shared with the host check and the plain-C++ drop-in.
+// The launch and the host result assembly are also lent to plba_match.hip (plba_verify_loop_candidates) through plba_relpose_launch.h.
 #include <vector>
 
 #include "plba_problem.h"
-#include "plba_relpose_dev.h"
+#include "plba_relpose_launch.h"
 
 namespace plba {
 namespace {
 
 namespace rp = relpose;
-constexpr int RP_OUT_D = 12 + 21 + 1 + 6 + 6;      // per candidate: T_inc (R, t), H (upper), e, logmap(T_inc), pose_inc
-constexpr int RP_OUT_I = 4;                        // n_inliers, iters[2], status
-
-struct RelposeDev {
-    rp::Opt o;
-    const int32_t *pt_start, *ln_start;
-    const double *P3, *uv2, *pq6, *l3, *T0;        // T0: B x 12 or null
-    uint8_t *pt_in, *ln_in;
-    double* out_d;
-    int32_t* out_i;
-};
 
 template <int CTRL>
 __device__ __forceinline__ double rp_dpp(double v) {
@@ -102,6 +92,52 @@ __global__ __launch_bounds__(64) void k_relpose(RelposeDev d) {
 size_t al8(size_t b) { return (b + 7) & ~(size_t)7; }
 
 }  // namespace
+
+void relpose_set_options(const plba_relpose_options& opt, double fx, double fy, double cx, double cy, relpose::Opt& o) {
+    o.max_iters = opt.max_iters; o.max_iters_ref = opt.max_iters_ref; o.protocol = opt.protocol; o.homog_th = opt.homog_th;
+    o.cut = sqrt(opt.chi2_th); o.fx = fx; o.fy = fy; o.cx = cx; o.cy = cy;
+}
+
+hipError_t relpose_launch(const RelposeDev& d, int B, hipStream_t s) {
+    hipLaunchKernelGGL(k_relpose, dim3((unsigned)B), dim3(64), 0, s, d);
+    return hipGetLastError();
+}
+
+// the uncertainty and the decision, on the host from what came back (:3593-3628, :3985-4021)
+void relpose_assemble(const plba_relpose_options& opt, int n_features, const double* q, const int32_t* oi, plba_relpose_result& r) {
+    const rp::Thresholds th{opt.lc_res, opt.lc_unc, opt.lc_inl, opt.lc_trs, opt.lc_rot};
+    rp::State st;
+    for (int i = 0; i < 9; ++i) st.T.R[i] = q[i];
+    for (int i = 0; i < 3; ++i) st.T.t[i] = q[9 + i];
+    for (int i = 0; i < 21; ++i) st.H[i] = q[12 + i];
+    st.e = q[33];
+    st.n_inl = oi[0]; st.iters[0] = oi[1]; st.iters[1] = oi[2]; st.status = oi[3];
+    rp::Decision dec;
+    rp::decide(st, q + 34, opt.protocol, n_features, th, dec);
+    for (int i = 0; i < 3; ++i) { r.T_inc16[i * 4] = q[i * 3]; r.T_inc16[i * 4 + 1] = q[i * 3 + 1]; r.T_inc16[i * 4 + 2] = q[i * 3 + 2]; r.T_inc16[i * 4 + 3] = q[9 + i]; }
+    r.T_inc16[12] = r.T_inc16[13] = r.T_inc16[14] = 0.0; r.T_inc16[15] = 1.0;
+    const bool ok = dec.status == PLBA_RELPOSE_OK || dec.status == PLBA_RELPOSE_RANK;
+    for (int i = 0; i < 6; ++i) r.pose_inc6[i] = ok ? q[40 + i] : 0.0;
+    int k = 0;
+    for (int i = 0; i < 6; ++i)
+        for (int j = i; j < 6; ++j) { r.H36[i * 6 + j] = q[12 + k]; r.H36[j * 6 + i] = q[12 + k]; ++k; }
+    r.e = st.e;
+    for (int i = 0; i < 6; ++i) r.cov_eig6[i] = dec.cov_eig[i];
+    r.t = dec.t; r.r = dec.r;
+    r.n_inliers = st.n_inl; r.iters[0] = st.iters[0]; r.iters[1] = st.iters[1];
+    r.status = dec.status; r.accepted = dec.accepted;
+    r.lc_res = dec.lc_res; r.lc_unc = dec.lc_unc; r.lc_inl = dec.lc_inl; r.lc_trs = dec.lc_trs; r.lc_rot = dec.lc_rot;
+}
+
+const char* relpose_check_options(const plba_relpose_options& opt, double fx, double fy, double cx, double cy) {
+    if (opt.protocol != 0 && opt.protocol != 1) return "protocol is not 0 or 1";
+    if (opt.max_iters < 0 || opt.max_iters_ref < 0) return "negative iteration count";
+    for (const double v : {opt.homog_th, opt.chi2_th, opt.lc_res, opt.lc_unc, opt.lc_inl, opt.lc_trs, opt.lc_rot, fx, fy, cx, cy})
+        if (!std::isfinite(v)) return "an option or an intrinsic is not finite";
+    if (opt.chi2_th < 0.0) return "chi2_th < 0";
+    return nullptr;
+}
+
 }  // namespace plba
 
 using namespace plba;
@@ -124,11 +160,7 @@ int plba_relative_pose(plba_problem* p, const plba_relpose_options* opt, int B, 
     if (!opt || !out) PLBA_FAIL(p, PLBA_ERR_INVALID, "plba_relative_pose: no options or no output");
     if (B < 1) PLBA_FAIL(p, PLBA_ERR_INVALID, "plba_relative_pose: B = %d", B);
     if (!pt_start || !ln_start) PLBA_FAIL(p, PLBA_ERR_INVALID, "plba_relative_pose: missing start array");
-    if (opt->protocol != 0 && opt->protocol != 1) PLBA_FAIL(p, PLBA_ERR_INVALID, "plba_relative_pose: protocol = %d", opt->protocol);
-    if (opt->max_iters < 0 || opt->max_iters_ref < 0) PLBA_FAIL(p, PLBA_ERR_INVALID, "plba_relative_pose: negative iteration count");
-    for (const double v : {opt->homog_th, opt->chi2_th, opt->lc_res, opt->lc_unc, opt->lc_inl, opt->lc_trs, opt->lc_rot, fx, fy, cx, cy})
-        if (!std::isfinite(v)) PLBA_FAIL(p, PLBA_ERR_INVALID, "plba_relative_pose: an option or an intrinsic is not finite");
-    if (opt->chi2_th < 0.0) PLBA_FAIL(p, PLBA_ERR_INVALID, "plba_relative_pose: chi2_th < 0");
+    if (const char* why = relpose_check_options(*opt, fx, fy, cx, cy)) PLBA_FAIL(p, PLBA_ERR_INVALID, "plba_relative_pose: %s", why);
     for (const int32_t* st : {pt_start, ln_start}) {
         if (st[0] != 0) PLBA_FAIL(p, PLBA_ERR_INVALID, "plba_relative_pose: a start array does not begin at 0");
         for (int b = 0; b < B; ++b) if (st[b + 1] < st[b]) PLBA_FAIL(p, PLBA_ERR_INVALID, "plba_relative_pose: the starts of candidate %d descend", b);
@@ -169,48 +201,21 @@ int plba_relative_pose(plba_problem* p, const plba_relpose_options* opt, int B, 
     PLBA_HIPCK(p, blk.alloc(total, false));
     PLBA_HIPCK(p, hipMemcpyAsync(blk.p, hu, up, hipMemcpyHostToDevice, s));
     RelposeDev d;
-    d.o.max_iters = opt->max_iters; d.o.max_iters_ref = opt->max_iters_ref; d.o.protocol = opt->protocol; d.o.homog_th = opt->homog_th;
-    d.o.cut = sqrt(opt->chi2_th); d.o.fx = fx; d.o.fy = fy; d.o.cx = cx; d.o.cy = cy;
+    relpose_set_options(*opt, fx, fy, cx, cy, d.o);
     d.pt_start = reinterpret_cast<const int32_t*>(blk.p + o_ps); d.ln_start = reinterpret_cast<const int32_t*>(blk.p + o_ls);
     d.P3 = reinterpret_cast<const double*>(blk.p + o_P); d.uv2 = reinterpret_cast<const double*>(blk.p + o_uv);
     d.pq6 = reinterpret_cast<const double*>(blk.p + o_pq); d.l3 = reinterpret_cast<const double*>(blk.p + o_l3);
     d.T0 = T0_16 ? reinterpret_cast<const double*>(blk.p + o_T0) : nullptr;
     d.pt_in = reinterpret_cast<uint8_t*>(blk.p + o_pm); d.ln_in = reinterpret_cast<uint8_t*>(blk.p + o_lm);
     d.out_d = reinterpret_cast<double*>(blk.p + o_od); d.out_i = reinterpret_cast<int32_t*>(blk.p + o_oi);
-    hipLaunchKernelGGL(k_relpose, dim3((unsigned)B), dim3(64), 0, s, d);
-    PLBA_HIPCK(p, hipGetLastError());
+    PLBA_HIPCK(p, relpose_launch(d, B, s));
     PLBA_HIPCK(p, hipMemcpyAsync(hd, blk.p + o_pm, down, hipMemcpyDeviceToHost, s));
     PLBA_HIPCK(p, plba_stream_wait(p, s));      // the call's one blocking wait
 
-    // the uncertainty and the decision, on the host from what came back (:3593-3628, :3985-4021)
-    const rp::Thresholds th{opt->lc_res, opt->lc_unc, opt->lc_inl, opt->lc_trs, opt->lc_rot};
     const double* od = reinterpret_cast<const double*>(hd + (o_od - o_pm));
     const int32_t* oi = reinterpret_cast<const int32_t*>(hd + (o_oi - o_pm));
-    for (int b = 0; b < B; ++b) {
-        const double* q = od + (size_t)RP_OUT_D * b;
-        plba_relpose_result& r = out[b];
-        rp::State st;
-        for (int i = 0; i < 9; ++i) st.T.R[i] = q[i];
-        for (int i = 0; i < 3; ++i) st.T.t[i] = q[9 + i];
-        for (int i = 0; i < 21; ++i) st.H[i] = q[12 + i];
-        st.e = q[33];
-        st.n_inl = oi[4 * (size_t)b]; st.iters[0] = oi[4 * (size_t)b + 1]; st.iters[1] = oi[4 * (size_t)b + 2]; st.status = oi[4 * (size_t)b + 3];
-        rp::Decision dec;
-        rp::decide(st, q + 34, opt->protocol, (pt_start[b + 1] - pt_start[b]) + (ln_start[b + 1] - ln_start[b]), th, dec);
-        for (int i = 0; i < 3; ++i) { r.T_inc16[i * 4] = q[i * 3]; r.T_inc16[i * 4 + 1] = q[i * 3 + 1]; r.T_inc16[i * 4 + 2] = q[i * 3 + 2]; r.T_inc16[i * 4 + 3] = q[9 + i]; }
-        r.T_inc16[12] = r.T_inc16[13] = r.T_inc16[14] = 0.0; r.T_inc16[15] = 1.0;
-        const bool ok = dec.status == PLBA_RELPOSE_OK || dec.status == PLBA_RELPOSE_RANK;
-        for (int i = 0; i < 6; ++i) r.pose_inc6[i] = ok ? q[40 + i] : 0.0;
-        int k = 0;
-        for (int i = 0; i < 6; ++i)
-            for (int j = i; j < 6; ++j) { r.H36[i * 6 + j] = q[12 + k]; r.H36[j * 6 + i] = q[12 + k]; ++k; }
-        r.e = st.e;
-        for (int i = 0; i < 6; ++i) r.cov_eig6[i] = dec.cov_eig[i];
-        r.t = dec.t; r.r = dec.r;
-        r.n_inliers = st.n_inl; r.iters[0] = st.iters[0]; r.iters[1] = st.iters[1];
-        r.status = dec.status; r.accepted = dec.accepted;
-        r.lc_res = dec.lc_res; r.lc_unc = dec.lc_unc; r.lc_inl = dec.lc_inl; r.lc_trs = dec.lc_trs; r.lc_rot = dec.lc_rot;
-    }
+    for (int b = 0; b < B; ++b)
+        relpose_assemble(*opt, (pt_start[b + 1] - pt_start[b]) + (ln_start[b + 1] - ln_start[b]), od + (size_t)RP_OUT_D * b, oi + (size_t)RP_OUT_I * b, out[b]);
     if (pt_inlier) memcpy(pt_inlier, hd, Np);
     if (ln_inlier) memcpy(ln_inlier, hd + (o_lm - o_pm), Nl);
     return PLBA_OK;
