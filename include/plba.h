@@ -115,7 +115,10 @@ typedef struct {
                                    stacked Jacobian and residual for plba_debug_get("marg_J") (the 40-digit fixture's input);
                                    bit 2 (fault injection, tests/test_lm_fused.py): the in-launch wait of k_lm_trial is given a count that
                                    never comes — the call must fail with PLBA_ERR_DEVICE, not hang; bit 3 (measurement / tests): the
-                                   Jacobi of the marginalization's kept block starts cold, without the tridiagonal pre-rotation    (0) */
+                                   Jacobi of the marginalization's kept block starts cold, without the tridiagonal pre-rotation;
+                                   bit 4 (tests): plba_compute_marginals keeps host copies of its pose system S as it stands before
+                                   the factorisation and of the full Sigma_pp, both P x P row-major, for plba_debug_get("cov_S") /
+                                   ("cov_Sigma"); two more blocking copies, the reported covariances keep their bits             (0) */
     int    pgo_solver;          /* linear solver of plba_optimize_pose_graph: 0 = dense Cholesky of the whole system; 1 = sparse
                                    multifrontal Cholesky (nested dissection, 6 x 6 blocks), for whole-map graphs; any other value:
                                    plba_optimize_pose_graph fails with PLBA_ERR_INVALID                                      (0) */
@@ -124,6 +127,7 @@ typedef struct {
 #define PLBA_DIAG_MARG_DUMP 2
 #define PLBA_DIAG_LEAD_WAIT_FAIL 4
 #define PLBA_DIAG_NO_MARG_PREROTATE 8
+#define PLBA_DIAG_COV_DUMP 16
 
 void plba_default_options(plba_options* o);
 
@@ -727,6 +731,8 @@ int  plba_verify_loop_candidates(plba_problem* p, const plba_loop_options* opt, 
  * "bl_ln" (Nl*6), "err_pvr" (M*9), "err_bias" (M*6), "err_prior" (n), "pose_dim" (1), "chi2" (1),
  * "maxdiag" (1); "marg_path" (5, after plba_marginalize*): [0] 0 = block-wise pseudo-inverse taken, 1 = dense
  * eigen-decomposition of Amm; [1..4] the certificate's w_max, smallest kept landmark eigenvalue, tau, smallest pivot;
+ * "cov_S", "cov_Sigma" (P*P row-major each, after a plba_compute_marginals under PLBA_DIAG_COV_DUMP; empty otherwise): the pose
+ * system S = Hpp - sum Hpl Hr^-1 Hlp as the device built it, and Sigma_pp = S^-1 as the device formed it, in the pose-side index order;
  * "host_waits" (1, at any time, waits for nothing): how often the library has blocked the calling thread on the device;
  * "pgo_sparse" (8, at any time): the last plba_optimize_pose_graph's solver (see there). */
 int plba_debug_build(plba_problem* p, double lambda, int do_solve);

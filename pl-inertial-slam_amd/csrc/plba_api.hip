@@ -47,7 +47,7 @@ static void reset_for_reuse(plba_problem* p, const plba_options* opt) {
     p->err[0] = 0;
     p->stream = p->ctx.stream; p->own_stream = true;
     p->ev_sample = false; p->trial_counter = 0; p->spec_lin = false; p->lin_in_span = false; p->prof_lin_launches = 0;
-    p->marg_dbg.clear(); for (double& v : p->marg_path) v = 0.0;
+    p->marg_dbg.clear(); p->cov_dbg_S.clear(); p->cov_dbg_Sigma.clear(); for (double& v : p->marg_path) v = 0.0;
     p->spec_hll = false;
     p->win.clear(); p->win_next.clear(); p->lm0.clear(); p->lm_fixed.clear();
     p->pr_n = p->pr_nv = 0; p->pr_vid.clear(); p->pr_size.clear(); p->pr_idx.clear(); p->pr_x0.clear(); p->pr_J0.clear(); p->pr_r0.clear();
@@ -2763,6 +2763,8 @@ int plba_debug_get(plba_problem* p, const char* what, double* out, size_t cap, s
     else if (w == "lm_groups") v = p->lm_hist;
     else if (w == "lm_fused") v = {(double)(p->lm_ok ? 1 : 0), (double)p->lv.ngrp, (double)p->lv.nblk, p->lm_ok && p->lm_hist.size() > 18 ? p->lm_hist[18] : 0.0 /* wide groups */};
     else if (w == "marg_J") v = p->marg_dbg;
+    else if (w == "cov_S") v = p->cov_dbg_S;
+    else if (w == "cov_Sigma") v = p->cov_dbg_Sigma;
     else if (w == "dense_dim") v = {(double)(p->chain_ok ? p->cv.Pd : p->P)};
     else if (w == "band") v = {(double)(p->band_ok ? 1 : 0)};
     else if (w == "twin") v = {(double)(p->twin_ok ? 1 : 0)};

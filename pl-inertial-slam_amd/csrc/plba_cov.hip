@@ -410,6 +410,15 @@ int cov_run(plba_problem* p, plba_marginals* m) {
     if (nblk) hipLaunchKernelGGL(k_cov_pairs, dim3(nblk), dim3(64), 0, s, dblk.p, dent.p, rec.p, S.p, Pp, d0.p);
     // 4. S = L L^T and N = L^-T on the matrix cores (launch_cholesky with the identity rows), N's last block column, the pivot test,
     //    Sigma_pp = N N^T
+    const bool dump = (p->opt.diag & PLBA_DIAG_COV_DUMP) != 0;      // host copies for plba_debug_get("cov_S" / "cov_Sigma"): read only, the launches are the same
+    auto keep = [&](const double* dev, std::vector<double>& dst) -> hipError_t {
+        std::vector<double> h((size_t)Pp * Pp);
+        const hipError_t e = plba_d2h(p, h.data(), dev, h.size() * 8);
+        dst.resize((size_t)P * P);
+        for (int r = 0; r < P; ++r) memcpy(dst.data() + (size_t)r * P, h.data() + (size_t)r * Pp, (size_t)P * 8);
+        return e;
+    };
+    if (dump) PLBA_HIPCK(p, keep(S.p, p->cov_dbg_S));
     DevBuf dd; memset(&dd, 0, sizeof dd);
     dd.P = P; dd.Ppad = Pp; dd.ld = Pp; dd.sys = S.p; dd.Lfac = Lfac.p; dd.ctrl = ctrl.p; dd.Linv = Linv.p; dd.flow_flags = flags.p;
     dd.LTblk = LT32.p; dd.Linv32 = LT32.p; dd.rdblk = rd32.p; dd.fb = 32; dd.chol_flags = cflags.p; dd.flow = 0; dd.wide = 0;
@@ -418,6 +427,7 @@ int cov_run(plba_problem* p, plba_marginals* m) {
     hipLaunchKernelGGL(k_cov_nlast, dim3((unsigned)(((size_t)Pp * CB + 255) / 256)), dim3(256), 0, s, dd);
     hipLaunchKernelGGL(k_cov_pivots, dim3(1), dim3(256), 0, s, dd, d0.p, fail.p);
     hipLaunchKernelGGL(k_cov_syrk, dim3(T, T), dim3(256), 0, s, Ninv.p, Pp, Pp, Sig.p);
+    if (dump) PLBA_HIPCK(p, keep(Sig.p, p->cov_dbg_Sigma));
     // 5. landmarks, 6. keyframe / pair blocks
     double* o_pt = out.p + n_out - L - (size_t)Nl * 36 - (size_t)Np * 9;
     double* o_ln = o_pt + (size_t)Np * 9;

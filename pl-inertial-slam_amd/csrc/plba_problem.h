@@ -250,6 +250,7 @@ struct plba_problem {
     bool lin_in_span = false;
     long prof_lin_launches = 0;     // profile = 2: k_linearize<true> launches whose time went into plba_stats.ms_phase[0], over the problem's life
     std::vector<double> marg_dbg;            // options.diag & PLBA_DIAG_MARG_DUMP: [R, pos, m, n, J (R x pos column-major), r (R)] of the last plba_marginalize* (tools/marg_exact_check.py)
+    std::vector<double> cov_dbg_S, cov_dbg_Sigma;   // options.diag & PLBA_DIAG_COV_DUMP: the P x P pose system before its factorisation and Sigma_pp of the last plba_compute_marginals (row-major)
     double marg_path[5] = {0, 0, 0, 0, 0};   // last plba_marginalize*: [0] 0 = block-wise pseudo-inverse, 1 = dense eigen-decomposition of Amm; [1..4] certificate: w_max, smallest kept landmark eigenvalue, tau, smallest pivot
     bool spec_hll = false;
     bool twin_ok = false;      // two-ended multi-launch factorisation of the compact dense system (plba_dense.hip: launch_twin_cholesky)

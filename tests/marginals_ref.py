@@ -52,6 +52,7 @@ class Reference:
         kw = w["kf"]
         K = len(kw["vid_pvr"])
         nav = [orc.nav_vec(kfs["P"][i], kfs["V"][i], kfs["q"][i], kw["bg"][i], kw["ba"][i], kfs["dbg"][i], kfs["dba"][i]) for i in range(K)]
+        self.nav = nav
         self.op_off, self.ob_off, self.P = pose_offsets(w)
         lvp = op.get_levels(0) if len(w["po_pt"]) else np.zeros(0, np.uint8)
         lvl = op.get_levels(1) if len(w["lo_ln"]) else np.zeros(0, np.uint8)
@@ -65,6 +66,7 @@ class Reference:
                 (0, Np, pts, w["po_pt"], w["po_kf"], w["po_uv"], w["po_w"], lvp, pfix),
                 (1, Nl, lns, w["lo_ln"], w["lo_kf"], w["lo_l"], w["lo_w"], lvl, lfix)):
             edges = [[] for _ in range(N)]
+            rho = [[] for _ in range(N)]      # Huber's rho' per kept edge (1 without a kernel)
             for e in range(len(lm_of)):
                 if lv[e]:
                     continue
@@ -80,8 +82,9 @@ class Reference:
                 if robust.get(kind) is not None:
                     rho1 = orc.huber(chi, robust[kind])[1]
                 edges[l].append((k, isg * rho1, Ji, Jj))
+                rho[l].append(float(rho1))
             for l in range(N):
-                self.lm.append(dict(kind=kind, idx=l, x=arr[l], fixed=bool(fix[l]), edges=edges[l]))
+                self.lm.append(dict(kind=kind, idx=l, x=arr[l], fixed=bool(fix[l]), edges=edges[l], rho1=rho[l]))
 
     def landmark_blocks(self, lm):
         """Hll, and per observation from a free keyframe (pose offset, Hpl block 9 x nd, Hpp block 9 x 9)."""

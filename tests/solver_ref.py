@@ -55,16 +55,22 @@ def _residual_mp(H, b, x):
     return r, s
 
 
-def refine(H, b, max_iter=40):
+def refine(H, b, max_iter=40, solve=None):
     """(x, omega): x solves H x = b to extended precision, as long double (a double-double pair folded into it where mpmath did the work);
-    omega = max_i |b - Hx|_i / (|H||x| + |b|)_i of the returned x, which the caller holds against RESIDUAL_MAX."""
+    omega = max_i |b - Hx|_i / (|H||x| + |b|)_i of the returned x, which the caller holds against RESIDUAL_MAX.
+    H given as long double is taken at that width in the residual (its fp64 rounding is factored for the corrections); solve: the
+    _Factor of H, for a caller that refines many right-hand sides of one matrix."""
+    Hw = H if (LD_IS_EXTENDED and getattr(H, "dtype", None) == LD) else None
     H = np.ascontiguousarray(H, dtype=np.float64); b = np.asarray(b, dtype=np.float64)
-    solve = _Factor(H)
+    if solve is None:
+        solve = _Factor(H)
     if LD_IS_EXTENDED:
+        if Hw is None:
+            Hw = H
         x = solve(b).astype(LD)
         best, best_x = np.inf, x
         for _ in range(max_iter):
-            r, s = _residual_ld(H, b, x)
+            r, s = _residual_ld(Hw, b, x)
             om = float(np.max(np.abs(r) / np.where(s > 0, s, LD(1))))
             if om >= best:
                 break

@@ -67,3 +67,20 @@ def test_reference_self_consistent(pkg, orc):
         assert np.abs(c[:3, :3] @ dv).max() <= 1e-9 * np.abs(c).max() and np.abs(c[3:, 3:] @ dv).max() <= 1e-9 * np.abs(c).max()
         assert np.linalg.matrix_rank(c, tol=1e-9 * np.abs(c).max()) == 4
     op.close()
+
+
+def test_recovered_hpp_equals_direct(pkg, orc):
+    """the Hpp the reference recovers through the damped Schur complement against the one tests/marginals_exact.py builds directly in
+    extended precision from the IMU, bias, prior and observation edges: the recovery's subtraction cancels, the direct sum does not"""
+    from tests import marginals_exact as mx
+    w = small_window(pkg)
+    op = orc.new_problem()
+    op.upload_window(w)
+    ex = mx.Exact(op, w, {k: w["huber"].get(k) for k in range(4)})
+    Hs = [ex.ref.hpp(op, lam) for lam in (1e-3, 10.0)]
+    op.close()
+    H = mx.narrow(ex.Hpp)
+    assert ex.P == 45 and np.abs(H).max() > 0
+    for Hr in Hs:
+        assert np.abs(Hr - H).max() <= 1e-10 * np.abs(H).max()
+    assert np.array_equal(ex.status, ex.ref.solve(Hs[0])["status"])
