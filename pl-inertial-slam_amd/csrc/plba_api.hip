@@ -1762,6 +1762,16 @@ static LmParams lm_params(const plba_problem* p) {
     return lp;
 }
 
+// In front of the first iteration of a call (plba_optimize, plba_debug_build): ONE launch resets the control block and clears what the
+// first passes add into — bimu, kfdiag, Himu at its structural positions (k_call_setup says why those are enough).  It replaces a
+// control-block kernel and three memsets (the one over all of Himu: 4.7 MB at configs[2], a tenth of it structural), each a launch of
+// its own on an empty stream.  Without an assembly list (chain_elim = 0) every entry of Himu is assembled, so all of it is cleared.
+static int enqueue_call_setup(plba_problem* p) {
+    const DevBuf& d = p->dv;
+    if (!d.alist) HIPCK(p, hipMemsetAsync(d.Himu, 0, (size_t)d.Ppad * d.ld * 8, p->stream));
+    launch_call_setup(d, p->stream);
+    return PLBA_OK;
+}
 // computeActiveErrors + buildSystem for the current estimate (everything lambda-independent)
 #define MARK(p, i) do { if ((p)->opt.profile >= 2) HIPCK(p, hipEventRecord((p)->ev[i], (p)->stream)); } while (0)
 // profile = 1 samples the factorisation span on every PROFILE_SAMPLE-th trial only: an event pair costs the stream ~8 us of
@@ -1772,10 +1782,8 @@ constexpr int PROFILE_SAMPLE = 8;
 static int enqueue_linearize(plba_problem* p, bool first_iter, int iteration) {
     const DevBuf& d = p->dv;
     hipStream_t s = p->stream;
-    if (first_iter) {   // later iterations start from the accumulator k_assemble cleared (swapped in on accept)
-        HIPCK(p, hipMemsetAsync(d.Himu, 0, (size_t)d.Ppad * d.ld * 8, s));
-        HIPCK(p, hipMemsetAsync(d.bimu, 0, (size_t)d.ld * 8, s));
-    }
+    // (first iteration: the accumulators were cleared by the call's set-up launch, enqueue_call_setup; later iterations start from the
+    // accumulator k_assemble cleared, swapped in on accept)
     MARK(p, 0);
     p->lin_in_span = !p->spec_lin;      // profile = 2: does the span between events 0 and 2 hold a k_linearize<true> launch?
     if (!p->spec_lin) launch_linearize(d, p->cur, true, p->rob, owns_pose_edges(p), s);   // observations + IMU / prior edges, one launch
@@ -1784,10 +1792,7 @@ static int enqueue_linearize(plba_problem* p, bool first_iter, int iteration) {
     if (p->spec_hll) p->assembled = true;      // the accepted trial's landmark blocks + assembly ran behind its deciding launch
     else p->assembled = launch_landmark_hll(d, p->cur, !first_iter, owns_pose_edges(p), s);
     p->spec_hll = false;
-    if (first_iter) {
-        HIPCK(p, hipMemsetAsync(d.kfdiag, 0, (size_t)d.K * 6 * 8, s));
-        launch_kfdiag(d, p->cur, p->world > 1, s);
-    }
+    if (first_iter) launch_kfdiag(d, p->cur, p->world > 1, s);      // (into the kfdiag the set-up launch cleared)
     // chi2 of the start state (and computeLambdaInit) is only needed on the first iteration of a call.  On later ones it
     // is the chi2 of the trial that was just accepted, evaluated on the very same state: k_decide left it in the control
     // block (already global in a sharded run) together with the iteration / trial counters, so neither the control
@@ -1871,11 +1876,12 @@ static int enqueue_solve(plba_problem* p, bool do_solve, bool need_dinv) {
 static int lm_enqueue_first(plba_problem* p, int iteration) {
     const DevBuf& d = p->dv;
     hipStream_t s = p->stream;
-    HIPCK(p, hipMemsetAsync(d.Himu, 0, (size_t)d.Ppad * d.ld * 8, s));
-    HIPCK(p, hipMemsetAsync(d.bimu, 0, (size_t)d.ld * 8, s));
-    HIPCK(p, hipMemsetAsync(d.kfdiag, 0, (size_t)d.K * 6 * 8, s));
-    MARK(p, 0);
-    launch_lm_schur(d, p->lv, p->cur, p->rob, true, nullptr, false, s, owns_pose_edges(p));      // (+ the pose-side edges, behind the groups)
+    MARK(p, 0);      // (Himu, bimu, kfdiag: cleared by the call's set-up launch, enqueue_call_setup)
+    // one GPU, short window, no per-phase events: lambda_init rides in the diagonal pass's last-arriving workgroup (diag_arrive) instead of
+    // in a one-workgroup launch behind it.  The long-window and the sharded form, and profile = 2 (its events 2 | 3 sit between the two), keep their launches.
+    const bool ride = p->world <= 1 && p->lv.nrow * 6 <= 256 && p->opt.profile < 2;
+    const LambdaInitFusion li{lm_params(p), p->d_red.p, iteration};
+    launch_lm_schur(d, p->lv, p->cur, p->rob, true, nullptr, false, s, owns_pose_edges(p), ride ? &li : nullptr);      // (+ the pose-side edges, behind the groups)
     MARK(p, 2);
     if (p->world > 1) {
         launch_lm_gather(d, p->lv, true, false, false, s);      // chi2 (sum), max |Hll_jj| (max) and the pose diagonal (sum) become global before computeLambdaInit, as on the record-based path
@@ -1893,7 +1899,7 @@ static int lm_enqueue_first(plba_problem* p, int iteration) {
         launch_reduce_n(d, true, p->d_red.p, p->lv.ngrp, s);
         launch_posediag(d, s);
         launch_lambda_init2(d, lm_params(p), p->d_red.p, true, iteration, false, false, s);
-    } else launch_lambda_init_n(d, p->lv, lm_params(p), p->d_red.p, iteration, p->lv.ngrp, s);      // (+ the diagonal gather)
+    } else if (!ride) launch_lambda_init_n(d, p->lv, lm_params(p), p->d_red.p, iteration, p->lv.ngrp, s);      // (+ the diagonal gather)
     MARK(p, 3);
     return PLBA_OK;
 }
@@ -1959,7 +1965,7 @@ int plba_optimize(plba_problem* p, int max_iters, const volatile uint8_t* abort_
     hipStream_t s = p->stream;
     plba_stats st;
     memset(&st, 0, sizeof st);
-    launch_ctrl_reset(d, s);      // (a kernel, not an upload + wait: the call starts without a synchronisation)
+    if ((rc = enqueue_call_setup(p))) return rc;      // (a kernel, not an upload + wait: the call starts without a synchronisation)
     ++p->state_epoch;
     p->trace.clear();
     const LmParams lp = lm_params(p);
@@ -2437,8 +2443,8 @@ int plba_save_state(plba_problem* p) {
     int rc = prepare(p);
     if (rc) return rc;
     HIPCK(p, hipSetDevice(p->device));
-    HIPCK(p, hipMemcpyAsync(p->d_kf_saved.p, p->dv.kf[p->cur], (size_t)p->win.K * KF_STRIDE * 8, hipMemcpyDeviceToDevice, p->stream));
-    if (p->L) HIPCK(p, hipMemcpyAsync(p->d_lm_saved.p, p->dv.lm[p->cur], (size_t)p->L * 6 * 8, hipMemcpyDeviceToDevice, p->stream));
+    launch_state_copy(p->d_kf_saved.p, p->dv.kf[p->cur], (size_t)p->win.K * KF_STRIDE, p->d_lm_saved.p, p->dv.lm[p->cur], (size_t)p->L * 6, p->stream);      // one launch, not two runtime copies
+    HIPCK(p, hipGetLastError());
     return PLBA_OK;
 }
 int plba_restore_state(plba_problem* p) {
@@ -2447,8 +2453,8 @@ int plba_restore_state(plba_problem* p) {
     if (rc) return rc;
     HIPCK(p, hipSetDevice(p->device));
     ++p->state_epoch;
-    HIPCK(p, hipMemcpyAsync(p->dv.kf[p->cur], p->d_kf_saved.p, (size_t)p->win.K * KF_STRIDE * 8, hipMemcpyDeviceToDevice, p->stream));
-    if (p->L) HIPCK(p, hipMemcpyAsync(p->dv.lm[p->cur], p->d_lm_saved.p, (size_t)p->L * 6 * 8, hipMemcpyDeviceToDevice, p->stream));
+    launch_state_copy(p->dv.kf[p->cur], p->d_kf_saved.p, (size_t)p->win.K * KF_STRIDE, p->dv.lm[p->cur], p->d_lm_saved.p, (size_t)p->L * 6, p->stream);
+    HIPCK(p, hipGetLastError());
     return PLBA_OK;
 }
 
@@ -2650,6 +2656,7 @@ int plba_debug_build(plba_problem* p, double lambda, int do_solve) {
     Ctrl c0;
     memset(&c0, 0, sizeof c0);
     c0.solver_ok = 1; c0.ni = 2.0;
+    if ((rc = enqueue_call_setup(p))) return rc;
     HIPCK(p, plba_h2d(p, d.ctrl, &c0, sizeof c0));
     if (p->lm_ok) {      // fused landmark-major passes, with the diagnostic outputs the parity tests read (Hll, bl, residuals, xl)
         p->lv.dbg_out = 1; p->lv.ob_err = p->d_ob_err.p;

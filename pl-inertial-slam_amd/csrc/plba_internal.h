@@ -101,7 +101,7 @@ struct DevBuf {  // trivially-copyable view of device pointers passed to kernels
     const int32_t* xlist;  // sharded runs: linear indices (r * ld + c, r >= c) of the lower-triangle entries that can be non-zero before the factorisation
     int nxlist;
     int* pair_cnt;         // arrival counters (indexed by a pair's first chunk slot), zero between launches
-    int* trial_cnt;        // arrival counter of the trial-error launch's workgroups (the last one decides), zero between launches
+    int* trial_cnt;        // arrival counter of the trial-error launch's workgroups (the last one decides) and of the diagonal pass's (the last one runs lambda_init), zero between launches
     unsigned* back_cnt;    // chain back-substitution segments finished, all k_lm_trial launches so far (monotonic; the launch's pose-side blocks wait for it)
     // IMU
     const int32_t *imu_i, *imu_j;
@@ -219,9 +219,11 @@ void launch_list_pack(const DevBuf& d, double* buf, bool unpack, hipStream_t s);
 void launch_tri_pack(const DevBuf& d, double* buf, bool unpack, hipStream_t s);
 void launch_lambda_init2(const DevBuf& d, const LmParams& lp, double* red, bool first_iter, int iteration, bool fused, bool keep_chi, hipStream_t s);
 void launch_decide(const DevBuf& d, const LmParams& lp, double* red, bool fused, Mailbox* mail, unsigned long long seq, hipStream_t s);
-void launch_ctrl_reset(const DevBuf& d, hipStream_t s);      // control block and trace counter of a fresh plba_optimize call
+void launch_call_setup(const DevBuf& d, hipStream_t s);      // control block and trace counter of a fresh plba_optimize call + bimu, kfdiag and the structural entries of Himu cleared
+void launch_state_copy(double* kf_dst, const double* kf_src, size_t nkf, double* lm_dst, const double* lm_src, size_t nlm, hipStream_t s);
 // fused landmark-major passes (plba_lm_dev.h)
-void launch_lm_schur(const DevBuf& d, const LmView& lv, int state, const Robust& rb, bool diag_pass, const ChainView* lead /* chain segments riding in front, or null */, bool spec, hipStream_t s, bool with_pose_edges = false);
+struct LambdaInitFusion { LmParams lp; double* red; int iteration; };      // the diagonal pass's last workgroup runs lambda_init (no launch_lambda_init_n behind it)
+void launch_lm_schur(const DevBuf& d, const LmView& lv, int state, const Robust& rb, bool diag_pass, const ChainView* lead /* chain segments riding in front, or null */, bool spec, hipStream_t s, bool with_pose_edges = false, const LambdaInitFusion* li = nullptr);
 void launch_lm_gather(const DevBuf& d, const LmView& lv, bool diag_pass, bool add_lambda, bool spec, hipStream_t s, const ChainView* wtw_cv = nullptr, const DevBuf* wtw_dd = nullptr);      // wtw_*: + the W^T W tiles of the chain Schur complement
 void launch_lm_trial(const DevBuf& d, const LmView& lv, int cur, int trial, bool jac, const Robust& rb, const ChainView* lead, const double* xd, unsigned back_target, bool with_pose_edges, const DecideFusion* df, hipStream_t s);
 void launch_reduce_n(const DevBuf& d, bool owns_pose_edges, double* red, int nred, hipStream_t s);

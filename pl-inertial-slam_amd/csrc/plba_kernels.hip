@@ -1415,7 +1415,7 @@ DEV void reduce_inline(const DevBuf& d, int nblk_edges, int nblk_lm, double* red
     for (int i = threadIdx.x; i < nblk_edges; i += 256) c += fetch(&d.chi_part[i], coherent);
     for (int i = threadIdx.x; i < d.M; i += 256) c += fetch(&d.imu_chi[(size_t)i * 4 + 2], coherent) + fetch(&d.imu_chi[(size_t)i * 4 + 3], coherent);
     if (threadIdx.x == 0 && d.pr_nv > 0) c += fetch(&d.pr_chi[0], coherent);
-    for (int i = threadIdx.x; i < nblk_lm; i += 256) { sc += d.scale_part[i]; md = fmax(md, d.maxd_part[i]); }
+    for (int i = threadIdx.x; i < nblk_lm; i += 256) { sc += d.scale_part[i]; md = fmax(md, fetch(&d.maxd_part[i], coherent)); }      // (scale_part: not this pass's, and not used by lambda_init)
     const double C = block_sum_256(c, s4);
     const double S = block_sum_256(sc, s4);
     const double Mx = block_max_256(md, s4);
@@ -1583,13 +1583,88 @@ __global__ __launch_bounds__(256) void k_cull(DevBuf d, int state, double thresh
 #include "plba_lm_dev.h"
 namespace plba {
 
+// first iteration of a call on the fused path, one GPU: what k_lm_gather's diagonal pass + k_lambda_init did in two launches — the groups'
+// diagonal parts summed per keyframe (fixed order), the pose diagonal, chi2, computeLambdaInit
+// (a device function: run by a launch of its own — k_lm_lambda_init — or by the last-arriving workgroup of the diagonal pass, diag_arrive;
+// coherent: the inputs were produced by other workgroups of the SAME launch, published with agent-scope stores / atomics, and are read
+// with agent-scope loads.  One body, one summation order: lambda has the same bits either way.)
+DEV void lm_lambda_init_body(const DevBuf& d, const LmView& lv, const LmParams& lp, double* red, int iteration, int nred, double* s4, double* s_part /* 256 */, bool coherent) {
+    reduce_inline(d, nred, nred, red, s4, coherent);
+    for (int r = threadIdx.x; r < d.ld; r += 256) d.posediag[r] = (r < d.P) ? fetch(&d.Himu[(size_t)r * d.ld + r], coherent) + d.Hconst[(size_t)r * d.ld + r] : 0.0;
+    __syncthreads();
+    // per keyframe and pose dimension: the groups' diagonal parts, the contributions dealt to nch lane groups (a small window has a
+    // dozen keyframes and hundreds of groups: one lane per entry walked them all, 40 us) and added in a fixed order
+    const int nent = lv.nrow * 6;
+    const int nch = nent > 0 && nent <= 128 ? 256 / nent : 1;
+    for (int base = 0; base < nent; base += 256) {
+        const int idx = base + (int)threadIdx.x % (nch > 1 ? nent : 256), ch = nch > 1 ? (int)threadIdx.x / nent : 0;
+        double v = 0.0;
+        const bool live = idx < nent && ch < nch;
+        int k = 0, c = 0;
+        if (live) {
+            k = idx / 6; c = idx - 6 * k;
+            for (int q = lv.row_start[k] + ch; q < lv.row_start[k + 1]; q += nch) {
+                const int src = lv.row_src[q];
+                v += fetch(&lv.part[(size_t)(src / lv.wmax) * lv.part_stride + lv.npair * 36 + (src % lv.wmax) * 12 + c], coherent);
+            }
+        }
+        if (nch > 1) {
+            s_part[threadIdx.x] = v;
+            __syncthreads();
+            if (live && ch == 0) { v = 0.0; for (int q = 0; q < nch; ++q) v += s_part[q * nent + idx]; }
+        }
+        if (live && ch == 0) {
+            const int kf = lv.row_kf[k], o = d.kf_off_pvr[kf];
+            d.kfdiag[kf * 6 + c] = v;
+            if (o >= 0) d.posediag[o + pmap(c)] += v;
+        }
+    }
+    __syncthreads();
+    double md = 0.0;
+    for (int r = threadIdx.x; r < d.P; r += 256) md = fmax(md, fabs(d.posediag[r]));
+    double mx = block_max_256(md, s4);
+    if (threadIdx.x == 0) {
+        Ctrl* c = d.ctrl;
+        c->current_chi = red[0];
+        c->iteration = iteration;
+        c->trial = 0;
+        mx = fmax(mx, red[2]);
+        c->maxdiag = mx;
+        c->lambda = lp.user_lambda > 0 ? lp.user_lambda : lp.tau * mx;
+        c->ni = 2.0;
+    }
+}
+__global__ __launch_bounds__(256) void k_lm_lambda_init(DevBuf d, LmView lv, LmParams lp, double* red, int iteration, int nred) {
+    __shared__ double s4[4];
+    __shared__ double s_part[256];
+    lm_lambda_init_body(d, lv, lp, red, iteration, nred, s4, s_part, false);
+}
+// The diagonal pass's own end (one GPU, short windows): every workgroup of k_lm_schur<1> — groups and pose-side edge blocks — ends here
+// once its partials are out (agent-scope stores: lm_schur_group's MODE 1 outputs, imu_chi, pr_chi; the IMU blocks' atomics into Himu),
+// counts itself in, and the last to arrive runs lambda_init: the trial launch's hand-off (trial_arrive: targeted, relaxed, arrive once
+// and never wait), on the same counter — the two launches are never in flight together, and the last arriver leaves it at zero.
+// lds: the workgroup's dynamic LDS, free by now (>= 36 KB): [s_part 256 | s4 4 | flag].
+struct DiagInit { LmParams lp; double* red; int iteration; int fuse; };
+DEV void diag_arrive(const DevBuf& d, const LmView& lv, const DiagInit& di, double* lds) {
+    int* s_last = reinterpret_cast<int*>(lds + 260);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int prev = __hip_atomic_fetch_add(d.trial_cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *s_last = (prev == (int)gridDim.x - 1) ? 1 : 0;
+        if (*s_last) __hip_atomic_store(d.trial_cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ready for the trial launch
+    }
+    __syncthreads();
+    if (!*s_last) return;
+    lm_lambda_init_body(d, lv, di.lp, di.red, di.iteration, lv.ngrp, lds + 256, lds, true);
+}
 // ---- fused landmark-major passes: kernels (bodies in plba_lm_dev.h) ------------------------------------------------------------------
 // launch C of an iteration: [chain segments, reading the pose-side accumulators directly (they carry no landmark term) | groups]
 // WIDE_OK: the instantiation that also carries the wide groups' code (landmarks over 9 .. 16 keyframes); a window without such landmarks
 // (lv.wmax == 8: every BASELINE config) runs the instantiation without it — inlined next to the standard groups' code the wide path cost
 // them registers (k_lm_schur<0> 24.7 -> 26.2 us at configs[2], profiles/r04_*), as a separate instantiation it costs nothing
 template <int MODE, bool WIDE_OK>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_lm_schur(DevBuf d, LmView lv, int state, Robust rb, ChainView cv, int nlead, int spec) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_lm_schur(DevBuf d, LmView lv, int state, Robust rb, ChainView cv, int nlead, int spec, DiagInit di) {
     if (spec && !d.ctrl->accepted) return;      // enqueued behind the deciding launch: runs only for the state that was accepted
     __shared__ LmLds S;
     extern __shared__ __attribute__((aligned(16))) double s_dyn_lm[];      // LmAcc (36 KB) | a chain segment's staging (48 KB)
@@ -1600,6 +1675,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const int m = b - lv.ngrp;
         if (m < d.M) pose_edge_block<true, 256>(d, state, rb, m, threadIdx.x);
         else prior_block<true>(d, state);
+        if (di.fuse) diag_arrive(d, lv, di, s_dyn_lm);
         return;
     }
     LmAcc& A4 = *reinterpret_cast<LmAcc*>(s_dyn_lm);
@@ -1608,6 +1684,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     else if (kind == 1) lm_schur_group<true, MODE>(d, lv, b, state, rb, S, A4);
     else if (WIDE_OK && kind == 2) lm_schur_group_wide<false, MODE>(d, lv, b, state, rb, S, A4);
     else if (WIDE_OK) lm_schur_group_wide<true, MODE>(d, lv, b, state, rb, S, A4);
+    if (MODE == 1 && di.fuse) diag_arrive(d, lv, di, s_dyn_lm);      // (+ lambda_init in the launch's last workgroup)
 }
 // launch D: [blocks assembling the part of the system no landmark touches | gather blocks: pose-pair blocks and right-hand-side rows =
 // pose-side terms + the groups' parts]
@@ -1680,22 +1757,24 @@ __global__ __launch_bounds__(LMB) void k_lm_trial(DevBuf d, LmView lv, int cur, 
 // -------------------------------------------------------------------------------------------------
 // launchers
 // -------------------------------------------------------------------------------------------------
-void launch_lm_schur(const DevBuf& d, const LmView& lv, int state, const Robust& rb, bool diag_pass, const ChainView* lead, bool spec, hipStream_t s, bool with_pose_edges) {
+void launch_lm_schur(const DevBuf& d, const LmView& lv, int state, const Robust& rb, bool diag_pass, const ChainView* lead, bool spec, hipStream_t s, bool with_pose_edges, const LambdaInitFusion* li) {
     const size_t sh = sizeof(LmAcc) > sizeof(ChainElimLds) ? sizeof(LmAcc) : sizeof(ChainElimLds);      // a chain segment's staging shares the dynamic LDS
     const bool wide = lv.wmax > LMF_W;
     if (diag_pass) {
         const void* fn = wide ? reinterpret_cast<const void*>(k_lm_schur<1, true>) : reinterpret_cast<const void*>(k_lm_schur<1, false>);
         if (ensure_dyn_lds(fn, (int)sh) != hipSuccess) return;      // surfaces at the caller's hipGetLastError
         const int npose = with_pose_edges ? d.M + (d.pr_nv > 0 ? 1 : 0) : 0;
-        if (wide) hipLaunchKernelGGL((k_lm_schur<1, true>), dim3(lv.ngrp + npose), dim3(256), sh, s, d, lv, state, rb, ChainView{}, 0, 0);
-        else hipLaunchKernelGGL((k_lm_schur<1, false>), dim3(lv.ngrp + npose), dim3(256), sh, s, d, lv, state, rb, ChainView{}, 0, 0);
+        DiagInit di{};
+        if (li) { di.lp = li->lp; di.red = li->red; di.iteration = li->iteration; di.fuse = 1; }
+        if (wide) hipLaunchKernelGGL((k_lm_schur<1, true>), dim3(lv.ngrp + npose), dim3(256), sh, s, d, lv, state, rb, ChainView{}, 0, 0, di);
+        else hipLaunchKernelGGL((k_lm_schur<1, false>), dim3(lv.ngrp + npose), dim3(256), sh, s, d, lv, state, rb, ChainView{}, 0, 0, di);
         return;
     }
     const void* fn = wide ? reinterpret_cast<const void*>(k_lm_schur<0, true>) : reinterpret_cast<const void*>(k_lm_schur<0, false>);
     if (ensure_dyn_lds(fn, (int)sh) != hipSuccess) return;
     const int nlead = lead ? lead->nseg : 0;
-    if (wide) hipLaunchKernelGGL((k_lm_schur<0, true>), dim3(lv.ngrp + nlead), dim3(256), sh, s, d, lv, state, rb, lead ? *lead : ChainView{}, nlead, spec ? 1 : 0);
-    else hipLaunchKernelGGL((k_lm_schur<0, false>), dim3(lv.ngrp + nlead), dim3(256), sh, s, d, lv, state, rb, lead ? *lead : ChainView{}, nlead, spec ? 1 : 0);
+    if (wide) hipLaunchKernelGGL((k_lm_schur<0, true>), dim3(lv.ngrp + nlead), dim3(256), sh, s, d, lv, state, rb, lead ? *lead : ChainView{}, nlead, spec ? 1 : 0, DiagInit{});
+    else hipLaunchKernelGGL((k_lm_schur<0, false>), dim3(lv.ngrp + nlead), dim3(256), sh, s, d, lv, state, rb, lead ? *lead : ChainView{}, nlead, spec ? 1 : 0, DiagInit{});
 }
 void launch_lm_gather(const DevBuf& d, const LmView& lv, bool diag_pass, bool add_lambda, bool spec, hipStream_t s, const ChainView* wtw_cv, const DevBuf* wtw_dd) {
     int nasm = 0;
@@ -1730,56 +1809,6 @@ void launch_reduce_n(const DevBuf& d, bool owns_pose_edges, double* red, int nre
 void launch_posediag(const DevBuf& d, hipStream_t s) {
     hipLaunchKernelGGL(k_posediag, dim3((d.ld + 255) / 256), dim3(256), 0, s, d);
     hipLaunchKernelGGL(k_posediag_kf, dim3((d.K * 6 + 255) / 256), dim3(256), 0, s, d);
-}
-// first iteration of a call on the fused path, one GPU: what k_lm_gather's diagonal pass + k_lambda_init did in two launches — the groups'
-// diagonal parts summed per keyframe (fixed order), the pose diagonal, chi2, computeLambdaInit
-__global__ __launch_bounds__(256) void k_lm_lambda_init(DevBuf d, LmView lv, LmParams lp, double* red, int iteration, int nred) {
-    __shared__ double s4[4];
-    __shared__ double s_part[256];
-    reduce_inline(d, nred, nred, red, s4);
-    for (int r = threadIdx.x; r < d.ld; r += 256) d.posediag[r] = (r < d.P) ? d.Himu[(size_t)r * d.ld + r] + d.Hconst[(size_t)r * d.ld + r] : 0.0;
-    __syncthreads();
-    // per keyframe and pose dimension: the groups' diagonal parts, the contributions dealt to nch lane groups (a small window has a
-    // dozen keyframes and hundreds of groups: one lane per entry walked them all, 40 us) and added in a fixed order
-    const int nent = lv.nrow * 6;
-    const int nch = nent > 0 && nent <= 128 ? 256 / nent : 1;
-    for (int base = 0; base < nent; base += 256) {
-        const int idx = base + (int)threadIdx.x % (nch > 1 ? nent : 256), ch = nch > 1 ? (int)threadIdx.x / nent : 0;
-        double v = 0.0;
-        const bool live = idx < nent && ch < nch;
-        int k = 0, c = 0;
-        if (live) {
-            k = idx / 6; c = idx - 6 * k;
-            for (int q = lv.row_start[k] + ch; q < lv.row_start[k + 1]; q += nch) {
-                const int src = lv.row_src[q];
-                v += lv.part[(size_t)(src / lv.wmax) * lv.part_stride + lv.npair * 36 + (src % lv.wmax) * 12 + c];
-            }
-        }
-        if (nch > 1) {
-            s_part[threadIdx.x] = v;
-            __syncthreads();
-            if (live && ch == 0) { v = 0.0; for (int q = 0; q < nch; ++q) v += s_part[q * nent + idx]; }
-        }
-        if (live && ch == 0) {
-            const int kf = lv.row_kf[k], o = d.kf_off_pvr[kf];
-            d.kfdiag[kf * 6 + c] = v;
-            if (o >= 0) d.posediag[o + pmap(c)] += v;
-        }
-    }
-    __syncthreads();
-    double md = 0.0;
-    for (int r = threadIdx.x; r < d.P; r += 256) md = fmax(md, fabs(d.posediag[r]));
-    double mx = block_max_256(md, s4);
-    if (threadIdx.x == 0) {
-        Ctrl* c = d.ctrl;
-        c->current_chi = red[0];
-        c->iteration = iteration;
-        c->trial = 0;
-        mx = fmax(mx, red[2]);
-        c->maxdiag = mx;
-        c->lambda = lp.user_lambda > 0 ? lp.user_lambda : lp.tau * mx;
-        c->ni = 2.0;
-    }
 }
 void launch_lambda_init_n(const DevBuf& d, const LmView& lv, const LmParams& lp, double* red, int iteration, int nred, hipStream_t s) {
     hipLaunchKernelGGL(k_lm_lambda_init, dim3(1), dim3(256), 0, s, d, lv, lp, red, iteration, nred);
@@ -1905,13 +1934,50 @@ void launch_reduce(const DevBuf& d, bool owns_pose_edges, double* red, hipStream
 void launch_lambda_init2(const DevBuf& d, const LmParams& lp, double* red, bool first_iter, int iteration, bool fused, bool keep_chi, hipStream_t s) {
     hipLaunchKernelGGL(k_lambda_init, dim3(1), dim3(256), 0, s, d, lp, red, first_iter ? 1 : 0, iteration, fused ? 1 : 0, keep_chi ? 1 : 0, d.E ? edge_blocks(d) : 0, d.L ? lm_blocks(d) : 0);
 }
-__global__ void k_ctrl_reset(Ctrl* c, int* trace_n) {
-    Ctrl z;
-    memset(&z, 0, sizeof z);
-    z.solver_ok = 1; z.ni = 2.0;
-    *c = z; *trace_n = 0;
+// The one launch in front of a plba_optimize call: the control block and trace counter of a fresh call, and the accumulators the first
+// iteration's passes add into — bimu, kfdiag, and Himu AT ITS STRUCTURAL POSITIONS ONLY (d.alist, the chain path's assembly list).
+// Why the list is enough: prepare() zero-fills both accumulators whole whenever it (re)creates them (every upload, structure-cache hit or
+// miss: DArr::alloc).  From then on Himu / Himu_alt are written by the IMU edge blocks' atomics alone — the 24 x 24 block over
+// [PVR_i | PVR_j | Bias_i] and the 12 x 12 one over [Bias_i | Bias_j] (pose_edge_block; the prior's Hessian is constant and lives in
+// Hconst) — and cleared by the assembly passes at list positions; d.alist was built at upload from exactly those blocks (add_full over
+// e1 / e2, plba_api.hip) plus the prior's and the pair blocks and the diagonal.  So an entry outside the list is zero since the upload and stays zero, whoever reads it, and an entry
+// a previous call left dirty — its last accepted linearisation, or a rejected trial's, in either accumulator — lies inside it.
+// Without a list (chain_elim = 0: the dense path assembles every entry) the caller clears Himu whole, as before.
+__global__ __launch_bounds__(256) void k_call_setup(DevBuf d) {
+    const size_t n = d.alist ? (size_t)d.nalist : 0, nb = (size_t)d.ld, nk = (size_t)d.K * 6;
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < n + nb + nk; k += stride) {
+        if (k < n) d.Himu[d.alist[k]] = 0.0;
+        else if (k < n + nb) d.bimu[k - n] = 0.0;
+        else d.kfdiag[k - n - nb] = 0.0;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        Ctrl z;
+        memset(&z, 0, sizeof z);
+        z.solver_ok = 1; z.ni = 2.0;
+        *d.ctrl = z; *d.trace_n = 0;
+    }
 }
-void launch_ctrl_reset(const DevBuf& d, hipStream_t s) { hipLaunchKernelGGL(k_ctrl_reset, dim3(1), dim3(1), 0, s, d.ctrl, d.trace_n); }
+void launch_call_setup(const DevBuf& d, hipStream_t s) {
+    const size_t n = (size_t)(d.alist ? d.nalist : 0) + (size_t)d.ld + (size_t)d.K * 6;
+    int blocks = (int)((n + 4 * 256 - 1) / (4 * 256));
+    if (blocks > 256) blocks = 256;
+    hipLaunchKernelGGL(k_call_setup, dim3(blocks), dim3(256), 0, s, d);
+}
+// plba_save_state / plba_restore_state: the keyframe and the landmark array in one launch
+__global__ __launch_bounds__(256) void k_state_copy(double* __restrict__ kf_dst, const double* __restrict__ kf_src, size_t nkf, double* __restrict__ lm_dst, const double* __restrict__ lm_src, size_t nlm) {
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < nkf + nlm; k += stride) {
+        if (k < nkf) kf_dst[k] = kf_src[k];
+        else lm_dst[k - nkf] = lm_src[k - nkf];
+    }
+}
+void launch_state_copy(double* kf_dst, const double* kf_src, size_t nkf, double* lm_dst, const double* lm_src, size_t nlm, hipStream_t s) {
+    int blocks = (int)((nkf + nlm + 4 * 256 - 1) / (4 * 256));
+    if (blocks > 1024) blocks = 1024;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(k_state_copy, dim3(blocks), dim3(256), 0, s, kf_dst, kf_src, nkf, lm_dst, lm_src, nlm);
+}
 void launch_decide(const DevBuf& d, const LmParams& lp, double* red, bool fused, Mailbox* mail, unsigned long long seq, hipStream_t s) {
     hipLaunchKernelGGL(k_decide, dim3(1), dim3(256), 0, s, d, lp, red, fused ? 1 : 0, d.E ? edge_blocks(d) : 0, d.L ? lm_blocks(d) : 0, mail, seq);
 }

@@ -452,11 +452,14 @@ DEV void lm_schur_group(const DevBuf& d, const LmView& lv, const int gidx, const
     }
     if ((int)threadIdx.x < LMF_W * 12 && (MODE == 0 || threadIdx.x % 12 < 6)) {
         const int p = threadIdx.x / 12, k = 21 + threadIdx.x % 12;
-        part[lv.npair * 36 + threadIdx.x] = (vs[(0 * LMF_W + p) * LMF_NVEC + k] + vs[(1 * LMF_W + p) * LMF_NVEC + k]) + (vs[(2 * LMF_W + p) * LMF_NVEC + k] + vs[(3 * LMF_W + p) * LMF_NVEC + k]);
+        const double pv = (vs[(0 * LMF_W + p) * LMF_NVEC + k] + vs[(1 * LMF_W + p) * LMF_NVEC + k]) + (vs[(2 * LMF_W + p) * LMF_NVEC + k] + vs[(3 * LMF_W + p) * LMF_NVEC + k]);
+        if (MODE == 1) publish(&part[lv.npair * 36 + threadIdx.x], pv);      // the diagonal pass: read by the launch's last workgroup (diag_arrive), as are its two partials below
+        else part[lv.npair * 36 + threadIdx.x] = pv;
     }
     if (threadIdx.x == 0) {
-        d.chi_part[gidx] = (S.red[0][0] + S.red[1][0]) + (S.red[2][0] + S.red[3][0]);
-        if (MODE == 1) d.maxd_part[gidx] = fmax(fmax(S.red[0][1], S.red[1][1]), fmax(S.red[2][1], S.red[3][1]));
+        const double cs = (S.red[0][0] + S.red[1][0]) + (S.red[2][0] + S.red[3][0]);
+        if (MODE == 1) { publish(&d.chi_part[gidx], cs); publish(&d.maxd_part[gidx], fmax(fmax(S.red[0][1], S.red[1][1]), fmax(S.red[2][1], S.red[3][1]))); }
+        else d.chi_part[gidx] = cs;
     }
 #ifdef PLBA_STAMPS_LMF
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -662,11 +665,14 @@ DEV void lm_schur_group_wide(const DevBuf& d, const LmView& lv, const int gidx, 
     }
     if ((int)threadIdx.x < LMF_W2 * 12 && (MODE == 0 || threadIdx.x % 12 < 6)) {
         const int pslot = threadIdx.x / 12, k = 21 + threadIdx.x % 12;
-        part[lv.npair * 36 + threadIdx.x] = (vs[(0 * LMF_W2 + pslot) * LMF_NVEC + k] + vs[(1 * LMF_W2 + pslot) * LMF_NVEC + k]) + (vs[(2 * LMF_W2 + pslot) * LMF_NVEC + k] + vs[(3 * LMF_W2 + pslot) * LMF_NVEC + k]);
+        const double pv = (vs[(0 * LMF_W2 + pslot) * LMF_NVEC + k] + vs[(1 * LMF_W2 + pslot) * LMF_NVEC + k]) + (vs[(2 * LMF_W2 + pslot) * LMF_NVEC + k] + vs[(3 * LMF_W2 + pslot) * LMF_NVEC + k]);
+        if (MODE == 1) publish(&part[lv.npair * 36 + threadIdx.x], pv);      // (see lm_schur_group)
+        else part[lv.npair * 36 + threadIdx.x] = pv;
     }
     if (threadIdx.x == 0) {
-        d.chi_part[gidx] = (S.red[0][0] + S.red[1][0]) + (S.red[2][0] + S.red[3][0]);
-        if (MODE == 1) d.maxd_part[gidx] = fmax(fmax(S.red[0][1], S.red[1][1]), fmax(S.red[2][1], S.red[3][1]));
+        const double cs = (S.red[0][0] + S.red[1][0]) + (S.red[2][0] + S.red[3][0]);
+        if (MODE == 1) { publish(&d.chi_part[gidx], cs); publish(&d.maxd_part[gidx], fmax(fmax(S.red[0][1], S.red[1][1]), fmax(S.red[2][1], S.red[3][1]))); }
+        else d.chi_part[gidx] = cs;
     }
 }
 
