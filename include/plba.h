@@ -724,6 +724,102 @@ int  plba_verify_loop_candidates(plba_problem* p, const plba_loop_options* opt, 
         double fx, double fy, double cx, double cy,
         int32_t* pt_match, int32_t* ln_match, uint8_t* pt_inlier, uint8_t* ln_inlier, plba_loop_result* out);
 
+/* ---- place recognition: bag-of-words transform, scoring and loop candidates ---------------------------
+ * The front half of MapHandler::loopClosure (src/mapHandler.cpp:3051-3114): insertKFBowVectorP / L / PL (:3116-3237) and
+ * lookForLoopCandidates (:3239-3299) with DBoW2's vocabulary tree, on the device, with a device-resident database of the keyframes'
+ * bag-of-words vectors.  Descriptors are 32 bytes (FORB, include/mapHandler.h:70); kind 0 = points (dbow_voc_p), 1 = lines (dbow_voc_l).
+ *
+ * plba_bow_set_vocabulary uploads one kind's tree once.  Node 0 is the root; parent[i] (i >= 1) must be in [0, i); a node's children
+ * are the nodes that name it as parent, in ascending node index (load()'s push_back order, 3rdparty/DBoW2/include/DBoW2/
+ * TemplatedVocabulary.h:1458-1471); a node without children is a leaf and carries word_id[i] in [0, n_nodes), unique; an inner
+ * node's word_id is not read (-1 by convention).  weight is WordValue, a double.  k and L are informative: the tree may be ragged.
+ * weighting is the WeightingType enum, 0 TF_IDF, 1 TF (values accumulate with addWeight), 2 IDF, 3 BINARY (addIfNotExist); the weights
+ * are used as given.  scoring: ONLY 0 (L1_NORM) is supported, any other value is refused with PLBA_ERR_INVALID.  The library lays the
+ * nodes out again breadth first, so that a node's children are contiguous (a pure host function, plba_bow_dev.h: plan_vocabulary).
+ * Setting a vocabulary of a kind drops the database.  Refused: kind not 0 / 1, weighting outside 0 .. 3, n_nodes < 2, a missing array,
+ * a malformed tree (parent[i] >= i or negative, a leaf without a word id, a word id >= n_nodes, a duplicate word id).
+ *
+ * plba_bow_transform (stateless): B sets of descriptors, CSR over B (set b owns rows [start[b], start[b+1]) of desc32).  word
+ * (start[B]): the word id of every descriptor, or -1 when the word's weight is not > 0 ("stopped", :1073).  The descent (:1198-1239):
+ * from the root, the child with the smallest Hamming distance, children visited in order and replaced on a strict `<` (the first of
+ * equal distances wins), down to a leaf.  Set b's vector is [start[b], start[b] + nnz[b]) of bow_id / bow_val (each start[B] long):
+ * word ids ascending, values accumulated as the weighting says, then L1-normalised (src/DBoW2/BowVector.cpp:62-84); a norm of 0 or an
+ * empty vector is left as it is.
+ *
+ * plba_bow_insert_keyframes appends B keyframes; they get the indices first_index = n_db .. n_db + B - 1 in order (append-only, as
+ * kf_idx is).  Per kind, CSR over B: the descriptors and the image positions of the dispersion term, one row each: points pl (2
+ * doubles), lines spl, epl (4 doubles; the midpoint is (spl + epl) * 0.5, :3203-3204).  Optional, CSR over B: cov, the covisibility
+ * column full_graph[i][idx] for i < idx (int32 >= 0; cov_start[b + 1] - cov_start[b] must be first_index + b).  Keyframe b is scored
+ * against every live keyframe with a smaller index, earlier members of the same call included.  opt->mode: 0 combined (:3166-3237),
+ * 1 points only (:3116-3139), 2 lines only (:3141-3164); a mode reads and stores only the kinds it uses (the other kind's arrays
+ * may be NULL, its stored vector is empty and its score 0).  Combined, literally: score = 0.0; score += (sp * n_pt + sl * n_ls) / n_pl;
+ * score += (sp * std_pt + sl * std_ls) / std_pl; std_* = vector_stdv(x) + vector_stdv(y) (stvo-pl/src/auxiliar.cpp:504-513, two
+ * passes, sqrt(1.0 / n * e)); n_* are the row counts.  An empty kind gives NaN through 0 / 0, as the text does; it is not guarded.
+ * Outputs (plba_bow_result; every array optional): row b of score_p / score_l / score (double) and score_f32 has first_index + b + 1
+ * entries, i = 0 .. idx, the last one the self-score (:3138, :3163, :3231-3236), and begins at b (first_index + 1) + b (b - 1) / 2;
+ * score_cap is the caller's capacity in entries.  score_f32 is the float the reference stores (conf_matrix, include/mapHandler.h:153),
+ * the rounding of the call's own double.  A removed keyframe's entries are 0.  pt_* / ln_*: the words, vectors and nnz as
+ * plba_bow_transform gives them over pt_start / ln_start.  With cov, cand[b] is lookForLoopCandidates on the float column, literally:
+ * eligible are the live i < idx - lc_kf_dist; lc_min_score starts at 1.0 and is taken over ALL i < idx, live or not, with
+ * cov[i] >= min_lm_cov_graph || idx - i <= min_kf_local_map + 3, updated where score_i < lc_min_score && score_i > 0.001; the best
+ * eligible needs score >= lc_min_score; n_closest counts the other eligible entries with abs(i - idx_max) <= lc_kf_max_dist &&
+ * score >= lc_min_score * 0.8 (the product in double) and is 0 when the best fails; is_candidate = n_eligible > lc_kf_max_dist &&
+ * best >= lc_min_score && n_closest >= lc_nkf_closest, kf_prev = idx_max then and -1 otherwise.  best_score, lc_min_score, n_closest
+ * and topk are reported whether or not n_eligible passes its test.  The reference finds the best entry with an unstable std::sort
+ * (:3260); its order is pinned HERE as: scan in ascending index, replace the current best on a strict `>`, so the lowest index wins a
+ * tie and a NaN never displaces anything; topk is that scan repeated over what is left (score descending, index ascending).  This
+ * rule is UNPINNED by the reference, as the matcher's tie rule is; it shows only on exact float ties and NaN.
+ * Sums: a word's value is its weight added once per occurrence; the norm is summed in ascending word id; a score, and the mean and the
+ * sum of squares of vector_stdv, in the lane-tree order of plba_bow_dev.h (64 strided chains, then pairwise rounds), which depends on
+ * the length of the summed list alone.
+ * plba_bow_remove_keyframe marks a keyframe dead (map_keyframes[i] = NULL, :3041-3042); its slot and index stay.  plba_bow_reset drops
+ * the database and keeps the vocabularies.  plba_debug_get("bow_db") (5, at any time): [n, n_live, nnz_p, nnz_l, bytes].
+ * Contract, as the matcher's: `p` supplies the device, the stream and the error text; the uploaded window, prior, trace and saved
+ * state are neither read nor written; an insert or a transform call makes one staged copy up, one back and one blocking wait
+ * (plba_debug_get("host_waits")); a keyframe's result does not depend on B, on its neighbours in the call or on how the database
+ * buffers grew; two identical sequences of calls give identical bits.  Refused with PLBA_ERR_INVALID and nothing changed, outputs and
+ * database alike: B < 1 or B > 32767, starts that do not begin at 0 or descend, a cov_start that does not fit, a missing array with a non-zero
+ * count, no vocabulary for a kind the call uses, more than 8192 descriptors of one kind in one keyframe, a negative option (all
+ * options are integers), a mode outside 0 .. 2, topk outside 0 .. 16, a negative cov, a score_cap too small, cov without cand, a
+ * keyframe index outside the database (remove). */
+typedef struct plba_bow_options {
+    int32_t mode;               /* 0 combined (insertKFBowVectorPL), 1 points, 2 lines                     (0) */
+    int32_t topk;               /* entries of plba_bow_candidate.topk to fill, 0 .. 16                      (8) */
+    int32_t lc_kf_dist;         /* SlamConfig::lcKFDist, src/slamConfig.cpp:80                             (50) */
+    int32_t lc_kf_max_dist;     /* SlamConfig::lcKFMaxDist, :81                                            (50) */
+    int32_t lc_nkf_closest;     /* SlamConfig::lcNKFClosest, :82                                            (4) */
+    int32_t min_lm_cov_graph;   /* SlamConfig::minLMCovGraph, :61                                          (75) */
+    int32_t min_kf_local_map;   /* SlamConfig::minKFLocalMap, :62                                           (3) */
+    int32_t reserved;
+} plba_bow_options;
+typedef struct plba_bow_candidate {
+    int32_t is_candidate, kf_prev;      /* lookForLoopCandidates' return value and kf_prev_idx (-1: none) */
+    int32_t n_closest, n_eligible;
+    double  best_score, lc_min_score;   /* the best eligible float entry (0 when none is eligible); the covisibility minimum */
+    int32_t topk[16];                   /* eligible keyframes, score descending, index ascending; -1 behind the last */
+    double  topk_score[16];             /* their float entries; 0 behind the last */
+} plba_bow_candidate;
+typedef struct plba_bow_result {
+    int32_t first_index, reserved;      /* out: the index keyframe 0 of the call received */
+    int64_t score_cap;                  /* in: entries each non-NULL score array can hold */
+    double *score_p, *score_l, *score;
+    float  *score_f32;
+    int32_t *pt_word, *pt_bow_id; double *pt_bow_val; int32_t *pt_nnz;
+    int32_t *ln_word, *ln_bow_id; double *ln_bow_val; int32_t *ln_nnz;
+    plba_bow_candidate* cand;           /* B; required with cov */
+} plba_bow_result;
+void plba_bow_default_options(plba_bow_options* o);
+int  plba_bow_set_vocabulary(plba_problem* p, int kind, int k, int L, int weighting, int scoring, int n_nodes,
+                             const int32_t* parent, const uint8_t* desc32, const double* weight, const int32_t* word_id);
+int  plba_bow_transform(plba_problem* p, int kind, int B, const int32_t* start, const uint8_t* desc32,
+                        int32_t* word, int32_t* bow_id, double* bow_val, int32_t* nnz);
+int  plba_bow_insert_keyframes(plba_problem* p, const plba_bow_options* opt, int B,
+                               const int32_t* pt_start, const uint8_t* pt_desc32, const double* pt_pl2,
+                               const int32_t* ln_start, const uint8_t* ln_desc32, const double* ln_spl_epl4,
+                               const int32_t* cov_start, const int32_t* cov, plba_bow_result* out);
+int  plba_bow_remove_keyframe(plba_problem* p, int kf);
+int  plba_bow_reset(plba_problem* p);
+
 /* ---- diagnostics used by the parity tests (not needed by a drop-in caller) ------------------- */
 /* Runs computeActiveErrors + buildSystem + setLambda(lambda) + Schur on the current state without
  * updating it, then exposes named internal buffers: "Hschur" (P*P row-major), "bschur" (P),
@@ -734,7 +830,9 @@ int  plba_verify_loop_candidates(plba_problem* p, const plba_loop_options* opt, 
  * "cov_S", "cov_Sigma" (P*P row-major each, after a plba_compute_marginals under PLBA_DIAG_COV_DUMP; empty otherwise): the pose
  * system S = Hpp - sum Hpl Hr^-1 Hlp as the device built it, and Sigma_pp = S^-1 as the device formed it, in the pose-side index order;
  * "host_waits" (1, at any time, waits for nothing): how often the library has blocked the calling thread on the device;
- * "pgo_sparse" (8, at any time): the last plba_optimize_pose_graph's solver (see there). */
+ * "pgo_sparse" (8, at any time): the last plba_optimize_pose_graph's solver (see there);
+ * "bow_db" (5, at any time): the place-recognition database, [keyframes, live keyframes, stored entries of the point vectors, of the
+ * line vectors, device bytes held]. */
 int plba_debug_build(plba_problem* p, double lambda, int do_solve);
 int plba_debug_get(plba_problem* p, const char* what, double* out, size_t cap, size_t* n);
 /* the same entry under its round-1 name (tests/test_gpu_parity.py); product code calls plba_dense_solve */

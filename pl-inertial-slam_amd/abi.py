@@ -138,6 +138,27 @@ class LoopResult(C.Structure):
                 ("inl_ratio_ls", C.c_double), ("relpose", RelposeResult)]
 
 
+class BowOptions(C.Structure):
+    """plba_bow_options of include/plba.h"""
+    _fields_ = [("mode", C.c_int32), ("topk", C.c_int32), ("lc_kf_dist", C.c_int32), ("lc_kf_max_dist", C.c_int32), ("lc_nkf_closest", C.c_int32),
+                ("min_lm_cov_graph", C.c_int32), ("min_kf_local_map", C.c_int32), ("reserved", C.c_int32)]
+
+
+class BowCandidate(C.Structure):
+    """plba_bow_candidate of include/plba.h"""
+    _fields_ = [("is_candidate", C.c_int32), ("kf_prev", C.c_int32), ("n_closest", C.c_int32), ("n_eligible", C.c_int32), ("best_score", C.c_double),
+                ("lc_min_score", C.c_double), ("topk", C.c_int32 * 16), ("topk_score", C.c_double * 16)]
+
+
+class BowResult(C.Structure):
+    """plba_bow_result of include/plba.h"""
+    _fields_ = [("first_index", C.c_int32), ("reserved", C.c_int32), ("score_cap", C.c_int64), ("score_p", c_double_p), ("score_l", c_double_p),
+                ("score", c_double_p), ("score_f32", C.POINTER(C.c_float)), ("pt_word", c_int32_p), ("pt_bow_id", c_int32_p), ("pt_bow_val", c_double_p),
+                ("pt_nnz", c_int32_p), ("ln_word", c_int32_p), ("ln_bow_id", c_int32_p), ("ln_bow_val", c_double_p), ("ln_nnz", c_int32_p),
+                ("cand", C.POINTER(BowCandidate))]
+
+
+BOW_COMBINED, BOW_POINTS, BOW_LINES = range(3)
 RELPOSE_OK, RELPOSE_EMPTY, RELPOSE_NONFINITE, RELPOSE_RANK = range(4)
 TRACK_OK, TRACK_NONFINITE, TRACK_RANK = 0, 2, 3
 TRACK_REFINED, TRACK_ROBUST, TRACK_FEW_BEFORE, TRACK_FEW_AFTER = range(4)
@@ -152,10 +173,12 @@ _P = C.c_void_p  # plba_problem*
 # (compute_marginals: the reference computes no marginals; the oracle has no such entry.  optimize_pose_graph: the oracle restates the
 # pose graph as orc_pgo, a checker entry of its own outside this table.  refine_landmarks: g2o's structure-only solver is a stub at the
 # reference's boundary; its checker is the numpy restatement tests/refine_ref.py.  relative_pose: its checker is tests/relpose_ref.py.
-# track_pose: its checker is tests/track_ref.py.  match_descriptors, verify_loop_candidates: their checker is tests/match_ref.py)
+# track_pose: its checker is tests/track_ref.py.  match_descriptors, verify_loop_candidates: their checker is tests/match_ref.py.
+# bow_*: their checker is tests/bow_ref.py)
 PRODUCT_ONLY = {"slide_window", "get_sizes", "marginalize_to_prior", "get_prior", "compute_marginals", "optimize_pose_graph",
                 "refine_default_options", "refine_landmarks", "relpose_default_options", "relative_pose", "track_default_options", "track_pose",
-                "match_default_options", "match_descriptors", "loop_default_options", "verify_loop_candidates"}
+                "match_default_options", "match_descriptors", "loop_default_options", "verify_loop_candidates",
+                "bow_default_options", "bow_set_vocabulary", "bow_transform", "bow_insert_keyframes", "bow_remove_keyframe", "bow_reset"}
 
 # name -> (restype, argtypes); every symbol plba.h declares
 SIGNATURES = {
@@ -222,6 +245,13 @@ SIGNATURES = {
     "verify_loop_candidates": (C.c_int, [_P, C.POINTER(LoopOptions), C.c_int, c_int32_p, c_uint8_p, c_double_p, c_int32_p, c_uint8_p, c_double_p,
                                          c_int32_p, c_uint8_p, c_double_p, c_int32_p, c_uint8_p, c_double_p, C.c_double, C.c_double, C.c_double, C.c_double,
                                          c_int32_p, c_int32_p, c_uint8_p, c_uint8_p, C.POINTER(LoopResult)]),
+    "bow_default_options": (None, [C.POINTER(BowOptions)]),
+    "bow_set_vocabulary": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_int32_p, c_uint8_p, c_double_p, c_int32_p]),
+    "bow_transform": (C.c_int, [_P, C.c_int, C.c_int, c_int32_p, c_uint8_p, c_int32_p, c_int32_p, c_double_p, c_int32_p]),
+    "bow_insert_keyframes": (C.c_int, [_P, C.POINTER(BowOptions), C.c_int, c_int32_p, c_uint8_p, c_double_p, c_int32_p, c_uint8_p, c_double_p, c_int32_p,
+                                       c_int32_p, C.POINTER(BowResult)]),
+    "bow_remove_keyframe": (C.c_int, [_P, C.c_int]),
+    "bow_reset": (C.c_int, [_P]),
     "optimize_pose_graph": (C.c_int, [_P, C.POINTER(PoseGraph), C.c_int, C.c_double, C.c_int, C.POINTER(Stats), C.POINTER(TraceRow), C.c_int, C.POINTER(C.c_int)]),
 }
 
@@ -905,6 +935,99 @@ class Problem:
             out[k] = np.array([getattr(r, k) for r in res[:B]], np.float64)
         out["relpose"] = _relpose_dict([r.relpose for r in res[:B]])
         return out
+
+    def bow_set_vocabulary(self, kind, voc, weighting=0, scoring=0):
+        """plba_bow_set_vocabulary: voc is a dict with parent (n,), desc (n, 32) uint8, weight (n,), word_id (n,) and optionally k, L; kind 0 =
+        points, 1 = lines.  Drops the database."""
+        parent, desc, weight, word = _i32(voc["parent"]), _u8(voc["desc"]).reshape(-1, 32), _f64(voc["weight"]), _i32(voc["word_id"])
+        n = len(parent)
+        if not (len(desc) == len(weight) == len(word) == n):
+            raise ValueError("the vocabulary's arrays differ in length")
+        self.call("bow_set_vocabulary", int(kind), int(voc.get("k", 0)), int(voc.get("L", 0)), int(weighting), int(scoring), n, _ip(parent), _up(desc), _dp(weight),
+                  _ip(word))
+
+    def bow_transform(self, kind, desc):
+        """plba_bow_transform: desc is a list of B (n, 32) uint8 arrays.  Returns a dict of lists over B: word (int32, -1: stopped), bow_id,
+        bow_val (the normalised vector, ids ascending)."""
+        st, D = _desc_csr(desc)
+        B, N = len(desc), int(st[-1])
+        word, ids, vals, nnz = np.full(max(N, 1), -2, np.int32), np.full(max(N, 1), -2, np.int32), np.zeros(max(N, 1)), np.full(max(B, 1), -2, np.int32)
+        self.call("bow_transform", int(kind), B, _ip(st), _up(D) if N else None, _ip(word), _ip(ids), _dp(vals), _ip(nnz))
+        return dict(word=[word[st[b]:st[b + 1]].copy() for b in range(B)], bow_id=[ids[st[b]:st[b] + nnz[b]].copy() for b in range(B)],
+                    bow_val=[vals[st[b]:st[b] + nnz[b]].copy() for b in range(B)])
+
+    def bow_insert_keyframes(self, kfs, cov=None, want_bow=False, want_scores=True, **opts):
+        """plba_bow_insert_keyframes: kfs is a list of B dicts — pdesc (n, 32), pl (n, 2), ldesc (m, 32), spl_epl (m, 4) (a missing key is an
+        empty kind); cov: None or a list of B int arrays, cov[b] the covisibility column of keyframe b (first_index + b entries); opts: the
+        fields of plba_bow_options.  Returns a dict: first_index, and lists over B of score_p, score_l, score (float64) and score_f32, each
+        idx + 1 long (not with want_scores=False: the columns are then not read back); with cov, the fields of plba_bow_candidate as arrays over B (topk: (B, 16)); with want_bow, pt / ln dicts as
+        bow_transform returns them."""
+        o = BowOptions()
+        self.lib.fn["bow_default_options"](C.byref(o))
+        for k, v in opts.items():
+            if k == "reserved" or not hasattr(o, k):
+                raise TypeError("unknown bow option %r" % k)
+            setattr(o, k, int(v))
+        B = len(kfs)
+        n0 = int(self.debug_get("bow_db")[0])
+
+        def csr(key, width):
+            arrs = [np.zeros((0, width)) if d.get(key) is None else _f64(d[key]).reshape(-1, width) for d in kfs]
+            start = np.zeros(len(arrs) + 1, np.int32)
+            start[1:] = np.cumsum([len(a) for a in arrs])
+            return start, (np.ascontiguousarray(np.concatenate(arrs)) if arrs else np.zeros((0, width)))
+        ps, DP = _desc_csr([d.get("pdesc") for d in kfs]); ps2, PL = csr("pl", 2)
+        ls, DL = _desc_csr([d.get("ldesc") for d in kfs]); ls2, SE = csr("spl_epl", 4)
+        if o.mode == BOW_COMBINED and not (np.array_equal(ps, ps2) and np.array_equal(ls, ls2)):
+            raise ValueError("a keyframe's descriptors and positions differ in length")
+        R = B * (n0 + 1) + B * (B - 1) // 2
+        Ra = max(R, 1) if want_scores else 1
+        sp, sl, sc, sf = np.zeros(Ra), np.zeros(Ra), np.zeros(Ra), np.zeros(Ra, np.float32)
+        r = BowResult()
+        r.score_cap = max(R, 1)
+        if want_scores:
+            r.score_p, r.score_l, r.score, r.score_f32 = _dp(sp), _dp(sl), _dp(sc), sf.ctypes.data_as(C.POINTER(C.c_float))
+        Np, Nl = int(ps[-1]), int(ls[-1])
+        keep = []
+        if want_bow:
+            for pre, N in (("pt", Np), ("ln", Nl)):
+                w, i, v, z = np.full(max(N, 1), -2, np.int32), np.full(max(N, 1), -2, np.int32), np.zeros(max(N, 1)), np.zeros(max(B, 1), np.int32)
+                keep.append((w, i, v, z))
+                setattr(r, pre + "_word", _ip(w)); setattr(r, pre + "_bow_id", _ip(i)); setattr(r, pre + "_bow_val", _dp(v)); setattr(r, pre + "_nnz", _ip(z))
+        cs = cv = cand = None
+        if cov is not None:
+            if len(cov) != B:
+                raise ValueError("cov must list one column per keyframe")
+            cols = [np.ascontiguousarray(c, dtype=np.int32).reshape(-1) for c in cov]
+            cs = np.zeros(B + 1, np.int32); cs[1:] = np.cumsum([len(c) for c in cols])
+            cv = np.ascontiguousarray(np.concatenate(cols + [np.zeros(1, np.int32)]))
+            cand = (BowCandidate * max(B, 1))()
+            r.cand = cand
+        up = lambda a: _up(a) if len(a) else None
+        dd = lambda a: _dp(a) if len(a) else None
+        self.call("bow_insert_keyframes", C.byref(o), B, _ip(ps), up(DP), dd(PL), _ip(ls), up(DL), dd(SE), _ip(cs), _ip(cv), C.byref(r))
+        row = lambda b: b * (n0 + 1) + b * (b - 1) // 2
+        out = dict(first_index=int(r.first_index))
+        for k, a in (("score_p", sp), ("score_l", sl), ("score", sc), ("score_f32", sf)) if want_scores else ():
+            out[k] = [a[row(b):row(b) + n0 + b + 1].copy() for b in range(B)]
+        if cand is not None:
+            for k in ("is_candidate", "kf_prev", "n_closest", "n_eligible"):
+                out[k] = np.array([getattr(c, k) for c in cand[:B]], np.int32)
+            for k in ("best_score", "lc_min_score"):
+                out[k] = np.array([getattr(c, k) for c in cand[:B]], np.float64)
+            out["topk"] = np.array([list(c.topk) for c in cand[:B]], np.int32).reshape(B, 16)
+            out["topk_score"] = np.array([list(c.topk_score) for c in cand[:B]], np.float64).reshape(B, 16)
+        if want_bow:
+            for (pre, st_), (w, i, v, z) in zip((("pt", ps), ("ln", ls)), keep):
+                out[pre] = dict(word=[w[st_[b]:st_[b + 1]].copy() for b in range(B)], bow_id=[i[st_[b]:st_[b] + z[b]].copy() for b in range(B)],
+                                bow_val=[v[st_[b]:st_[b] + z[b]].copy() for b in range(B)])
+        return out
+
+    def bow_remove_keyframe(self, kf):
+        self.call("bow_remove_keyframe", int(kf))
+
+    def bow_reset(self):
+        self.call("bow_reset")
 
     def preintegrate(self, sample_start, t, gyr, acc, t_prev, t_curr, bg, ba, gyr_meas_cov, acc_meas_cov):
         """KeyFrame::ComputeIMUPreIntSinceLastFrame for M intervals (plba_preintegrate); time stamps as np.longdouble."""

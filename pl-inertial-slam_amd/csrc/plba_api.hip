@@ -43,6 +43,7 @@ static const size_t PARK_MAX = 2;
 // structure cache stay
 static void reset_for_reuse(plba_problem* p, const plba_options* opt) {
     marg_discard(p);      // (plba_destroy has done so already)
+    plba_bow_discard(p);
     if (opt) p->opt = *opt; else plba_default_options(&p->opt);
     p->err[0] = 0;
     p->stream = p->ctx.stream; p->own_stream = true;
@@ -189,6 +190,7 @@ void plba_destroy(plba_problem* p) {
     (void)hipSetDevice(p->device);
     marg_discard(p);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
+    plba_bow_discard(p);
     if (p->have_ctx) {
         (void)hipStreamSynchronize(p->ctx.stream);
         std::lock_guard<std::mutex> g(g_ctx_mu);
@@ -2699,6 +2701,13 @@ int plba_debug_get(plba_problem* p, const char* what, double* out, size_t cap, s
     if (w == "pgo_sparse") {      // (host-side record of the last plba_optimize_pose_graph: the pose graph uploads no window)
         if (n) *n = 8;
         for (size_t i = 0; out && i < cap && i < 8; ++i) out[i] = p->pgo_sparse[i];
+        return PLBA_OK;
+    }
+    if (w == "bow_db") {          // (host-side record of the place-recognition database)
+        double d5[5];
+        plba_bow_describe(p, d5);
+        if (n) *n = 5;
+        for (size_t i = 0; out && i < cap && i < 5; ++i) out[i] = d5[i];
         return PLBA_OK;
     }
     if (p->dirty) FAIL(p, PLBA_ERR_STATE, "debug_get before debug_build/optimize");

@@ -202,6 +202,7 @@ struct DArr {
 
 namespace plba {
 struct MargPending;      // a plba_marginalize_to_prior still in the stream (plba_marg.hip)
+struct BowState;         // the vocabularies and the keyframe database of place recognition (plba_bow.hip)
 // host image of the fused landmark-major passes' group structure (build_lm_groups, plba_api.hip); kept with the cached context
 // (HostCtx) so that its tables are not re-allocated (and their pages not re-faulted) by every BA call
 struct LmHost {
@@ -297,6 +298,7 @@ struct plba_problem {
     int pr_m = 0;                         // dropped dimension of the device-made prior (plba_get_prior)
     plba::MargPending* mp = nullptr;      // the marginalization that makes it, while it may still be in the stream (resolved by its first consumer)
     double pgo_sparse[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // last plba_optimize_pose_graph (plba_debug_get "pgo_sparse", include/plba.h)
+    plba::BowState* bow = nullptr;        // place recognition (plba_bow_*): made by the first plba_bow_set_vocabulary, dropped by plba_bow_discard()
     long host_waits = 0;                  // times the library blocked the calling thread on the device (plba_debug_get "host_waits")
     plba::Robust rob;
     // shard
@@ -445,6 +447,10 @@ inline hipError_t plba_h2d(plba_problem* p, void* dst_dev, const void* src, size
     }
     return hipSuccess;
 }
+
+// plba_bow.hip: frees the vocabularies and the database (the owner has synchronised the stream); plba_debug_get("bow_db")
+void plba_bow_discard(plba_problem* p);
+void plba_bow_describe(const plba_problem* p, double out5[5]);
 
 #define PLBA_FAIL(p, code, ...)                             \
     do {                                                    \
