@@ -17,11 +17,10 @@
 // The database keeps, per kind, one pool of ids and one of values, a keyframe's vector at the offset its descriptor rows gave it (a
 // vector has at most as many entries as the keyframe has descriptors, so the offsets are known before the device has counted), and
 // (offset, nnz) per keyframe.  The pools grow geometrically by a copy on the stream; the blocks they leave are released after the
-// call's wait.  The arithmetic is plba_bow_dev.h, shared with the host check and include/plba_g2o/bow.h.
-#include <vector>
-
+// call's wait.  The arithmetic is plba_bow_dev.h, shared with the host check and include/plba_g2o/bow.h.  The host side of the
+// transform and the insert (one block, one copy up, one down, one wait) is plba_batch_call.h's.
+#include "plba_batch_call.h"
 #include "plba_bow_dev.h"
-#include "plba_problem.h"
 
 namespace plba {
 
@@ -417,30 +416,9 @@ __global__ __launch_bounds__(256) void k_bow_decide(DecideDev d) {
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
-size_t al16(size_t b) { return (b + 15) & ~(size_t)15; }
-struct Layout {
-    size_t off = 0;
-    size_t take(size_t bytes) { const size_t o = off; off += al16(bytes); return o; }
-};
-struct Staged {      // staging memory of a call: the pinned area when it is there and large enough, pageable stand-ins otherwise
-    std::vector<char> h_up, h_down;
-    char *up = nullptr, *down = nullptr;
-    void take(size_t n_up, size_t n_down) {
-        up = (char*)stage_take(n_up); down = (char*)stage_take(n_down);
-        if (!up) { h_up.resize(n_up); up = h_up.data(); }
-        if (!down) { h_down.resize(n_down); down = h_down.data(); }
-    }
-};
-
-// what is wrong with a CSR start array over B sets of at most MAX_DESC rows, or null
-const char* check_starts(int B, const int32_t* st) {
-    if (st[0] != 0) return "a start array does not begin at 0";
-    for (int b = 0; b < B; ++b) {
-        if (st[b + 1] < st[b]) return "a start array descends";
-        if (st[b + 1] - st[b] > bw::MAX_DESC) return "more than 8192 descriptors of one kind in one keyframe";
-    }
-    return nullptr;
-}
+// the text for a keyframe with more than bw::MAX_DESC rows of one kind
+constexpr const char* TOO_MANY_DESC = "more than 8192 descriptors of one kind in one keyframe";
+static_assert(bw::MAX_DESC == 8192, "TOO_MANY_DESC names the limit");
 int max_rows(int B, const int32_t* st) {
     int m = 0;
     for (int b = 0; b < B; ++b) m = std::max(m, st[b + 1] - st[b]);
@@ -556,7 +534,7 @@ int plba_bow_transform(plba_problem* p, int kind, int B, const int32_t* start, c
     if (kind != 0 && kind != 1) PLBA_FAIL(p, PLBA_ERR_INVALID, "plba_bow_transform: kind = %d", kind);
     if (B < 1 || B > 32767) PLBA_FAIL(p, PLBA_ERR_INVALID, "plba_bow_transform: B = %d is outside 1 .. 32767", B);
     if (!start || !nnz) PLBA_FAIL(p, PLBA_ERR_INVALID, "plba_bow_transform: missing start array or nnz");
-    if (const char* why = check_starts(B, start)) PLBA_FAIL(p, PLBA_ERR_INVALID, "plba_bow_transform: %s", why);
+    if (const char* why = check_starts(B, start, bw::MAX_DESC, TOO_MANY_DESC)) PLBA_FAIL(p, PLBA_ERR_INVALID, "plba_bow_transform: %s", why);
     const size_t N = (size_t)start[B];
     if (N && (!desc32 || !word || !bow_id || !bow_val)) PLBA_FAIL(p, PLBA_ERR_INVALID, "plba_bow_transform: missing array");
     if (!p->bow || !p->bow->voc[kind].set) PLBA_FAIL(p, PLBA_ERR_INVALID, "plba_bow_transform: no vocabulary of kind %d", kind);
@@ -564,35 +542,26 @@ int plba_bow_transform(plba_problem* p, int kind, int B, const int32_t* start, c
     std::vector<int32_t> zero((size_t)B + 1, 0);
     // one device block: [starts | empty starts | desc || words | ids | values | nnz]; up: before the bar, down: behind it
     Layout L;
-    const size_t o_st = L.take(4 * ((size_t)B + 1)), o_z = L.take(4 * ((size_t)B + 1)), o_d = L.take(32 * N), up = L.off, o_w = L.take(4 * N), o_id = L.take(4 * N),
-                 o_val = L.take(8 * N), o_nnz = L.take(8 * (size_t)B), total = L.off;
-    const size_t down = total - up;
-    PLBA_HIPCK(p, hipSetDevice(p->device));
-    hipStream_t s = p->stream;
-    DArrStreamScope staged(s, p->have_ctx ? p->ctx.stage : nullptr);
-    Staged sg;
-    sg.take(up, down);
-    memcpy(sg.up + o_st, start, 4 * ((size_t)B + 1)); memcpy(sg.up + o_z, zero.data(), 4 * ((size_t)B + 1));
-    if (N) memcpy(sg.up + o_d, desc32, 32 * N);
-    DArr<char> blk;
-    PLBA_HIPCK(p, blk.alloc(total, false));
-    PLBA_HIPCK(p, hipMemcpyAsync(blk.p, sg.up, up, hipMemcpyHostToDevice, s));
-    auto i32 = [&](size_t o) { return reinterpret_cast<int32_t*>(blk.p + o); };
+    const size_t n_st = 4 * ((size_t)B + 1);
+    const size_t o_st = L.take(n_st), o_z = L.take(n_st), o_d = L.take(32 * N), up_end = L.off, o_w = L.take(4 * N), o_id = L.take(4 * N), o_val = L.take(8 * N),
+                 o_nnz = L.take(8 * (size_t)B);
+    BatchCall call(p);
+    PLBA_TRY(call.open(L.off, up_end, up_end, L.off));
+    call.put(o_st, start, n_st); call.put(o_z, zero.data(), n_st); call.put(o_d, desc32, 32 * N);
+    PLBA_TRY(call.upload());
     DescendDev t{};
     t.vp = voc_dev(st->voc[0]); t.vl = voc_dev(st->voc[1]);
-    t.desc = reinterpret_cast<const uint4*>(blk.p + o_d); t.Np = kind ? 0 : (int)N; t.Nl = kind ? (int)N : 0; t.word = i32(o_w);
+    t.desc = call.dev<uint4>(o_d); t.Np = kind ? 0 : (int)N; t.Nl = kind ? (int)N : 0; t.word = call.dev<int32_t>(o_w);
     BuildDev bd{};
     bd.B = B; bd.n0 = 0; bd.Np = 0; bd.NP = pow2_at_least(std::max(max_rows(B, start), 1));
-    bd.start_p = kind ? i32(o_z) : i32(o_st); bd.start_l = kind ? i32(o_st) : i32(o_z);
+    bd.start_p = call.dev<int32_t>(kind ? o_z : o_st); bd.start_l = call.dev<int32_t>(kind ? o_st : o_z);
     bd.word = t.word; bd.ww_p = t.vp.word_weight; bd.ww_l = t.vl.word_weight;
     bd.acc_p = bw::accumulates(t.vp.weighting); bd.acc_l = bw::accumulates(t.vl.weighting);
-    bd.out_id = i32(o_id); bd.out_val = reinterpret_cast<double*>(blk.p + o_val); bd.out_nnz = i32(o_nnz);
-    PLBA_HIPCK(p, transform_launch(t, bd, s));
-    PLBA_HIPCK(p, hipMemcpyAsync(sg.down, blk.p + up, down, hipMemcpyDeviceToHost, s));
-    PLBA_HIPCK(p, plba_stream_wait(p, s));      // the call's one blocking wait
-    const char* hd = sg.down;
-    if (N) { memcpy(word, hd + (o_w - up), 4 * N); memcpy(bow_id, hd + (o_id - up), 4 * N); memcpy(bow_val, hd + (o_val - up), 8 * N); }
-    memcpy(nnz, hd + (o_nnz - up) + (kind ? 4 * (size_t)B : 0), 4 * (size_t)B);
+    bd.out_id = call.dev<int32_t>(o_id); bd.out_val = call.dev<double>(o_val); bd.out_nnz = call.dev<int32_t>(o_nnz);
+    PLBA_HIPCK(p, transform_launch(t, bd, call.s));
+    PLBA_TRY(call.download());
+    if (N) { memcpy(word, call.down<int32_t>(o_w), 4 * N); memcpy(bow_id, call.down<int32_t>(o_id), 4 * N); memcpy(bow_val, call.down<double>(o_val), 8 * N); }
+    memcpy(nnz, call.down<int32_t>(o_nnz) + (kind ? (size_t)B : 0), 4 * (size_t)B);
     return PLBA_OK;
 }
 
@@ -611,7 +580,7 @@ int plba_bow_insert_keyframes(plba_problem* p, const plba_bow_options* opt, int 
     std::vector<int32_t> zero((size_t)B + 1, 0);
     const int32_t *ps = use_p ? pt_start : zero.data(), *ls = use_l ? ln_start : zero.data();
     for (const int32_t* st : {ps, ls})
-        if (const char* why = check_starts(B, st)) PLBA_FAIL(p, PLBA_ERR_INVALID, "plba_bow_insert_keyframes: %s", why);
+        if (const char* why = check_starts(B, st, bw::MAX_DESC, TOO_MANY_DESC)) PLBA_FAIL(p, PLBA_ERR_INVALID, "plba_bow_insert_keyframes: %s", why);
     const size_t Np = (size_t)ps[B], Nl = (size_t)ls[B];
     const bool want_std = opt->mode == bw::MODE_COMBINED;
     if ((Np && (!pt_desc32 || (want_std && !pt_pl2))) || (Nl && (!ln_desc32 || (want_std && !ln_spl_epl4))))
@@ -633,97 +602,86 @@ int plba_bow_insert_keyframes(plba_problem* p, const plba_bow_options* opt, int 
         PLBA_FAIL(p, PLBA_ERR_INVALID, "plba_bow_insert_keyframes: score_cap = %lld, the call writes %zu entries", (long long)out->score_cap, R);
 
     // one device block: [starts | live | desc | positions | cov || words | ids | values | nnz | stat | cand | float | score | score_p | score_l];
-    // up: before the bar, down: behind it
+    // up: before the bar; down: behind it, as far as the last score column the caller asked for
     Layout L;
-    const size_t o_ps = L.take(4 * ((size_t)B + 1)), o_ls = L.take(4 * ((size_t)B + 1)), o_live = L.take((size_t)n0), o_d = L.take(32 * (Np + Nl)),
-                 o_pp = L.take(want_std ? 16 * Np : 0), o_pl = L.take(want_std ? 32 * Nl : 0), o_cov = L.take(decide ? 4 * C : 0), up = L.off;
+    const size_t n_st = 4 * ((size_t)B + 1);
+    const size_t o_ps = L.take(n_st), o_ls = L.take(n_st), o_live = L.take((size_t)n0), o_d = L.take(32 * (Np + Nl)), o_pp = L.take(want_std ? 16 * Np : 0),
+                 o_pl = L.take(want_std ? 32 * Nl : 0), o_cov = L.take(decide ? 4 * C : 0), up_end = L.off;
     const size_t o_w = L.take(4 * (Np + Nl)), o_id = L.take(4 * (Np + Nl)), o_val = L.take(8 * (Np + Nl)), o_nnz = L.take(8 * (size_t)B), o_stat = L.take(16 * (size_t)B),
                  o_ci = L.take(4 * (size_t)CAND_I * B), o_cd = L.take(8 * (size_t)CAND_D * B), o_sf = L.take(4 * R), o_s = L.take(8 * R), o_sp = L.take(8 * R),
-                 o_sl = L.take(8 * R), total = L.off;
+                 o_sl = L.take(8 * R);
     // (the score columns are the bulk of a large database's read-back: a caller that asks for none of them gets none copied)
-    const size_t down = ((out->score_p || out->score_l) ? total : out->score ? o_sp : out->score_f32 ? o_s : o_sf) - up;
-    PLBA_HIPCK(p, hipSetDevice(p->device));
-    hipStream_t s = p->stream;
-    DArrStreamScope staged(s, p->have_ctx ? p->ctx.stage : nullptr);
-    Staged sg;
-    sg.take(up, down);
-    char* hu = sg.up;
-    memcpy(hu + o_ps, ps, 4 * ((size_t)B + 1)); memcpy(hu + o_ls, ls, 4 * ((size_t)B + 1));
-    if (n0) memcpy(hu + o_live, st->live.data(), (size_t)n0);
-    if (Np) memcpy(hu + o_d, pt_desc32, 32 * Np);
-    if (Nl) memcpy(hu + o_d + 32 * Np, ln_desc32, 32 * Nl);
-    if (want_std && Np) memcpy(hu + o_pp, pt_pl2, 16 * Np);
-    if (want_std && Nl) memcpy(hu + o_pl, ln_spl_epl4, 32 * Nl);
-    if (decide && C) memcpy(hu + o_cov, cov, 4 * C);
-    DArr<char> blk, old[6];
-    PLBA_HIPCK(p, blk.alloc(total, false));
-    PLBA_HIPCK(p, hipMemcpyAsync(blk.p, hu, up, hipMemcpyHostToDevice, s));
+    const size_t down_end = (out->score_p || out->score_l) ? L.off : out->score ? o_sp : out->score_f32 ? o_s : o_sf;
+    BatchCall call(p);
+    PLBA_TRY(call.open(L.off, up_end, up_end, down_end));
+    hipStream_t s = call.s;
+    call.put(o_ps, ps, n_st); call.put(o_ls, ls, n_st); call.put(o_live, st->live.data(), (size_t)n0);
+    call.put(o_d, pt_desc32, 32 * Np); call.put(o_d + 32 * Np, ln_desc32, 32 * Nl);
+    if (want_std) { call.put(o_pp, pt_pl2, 16 * Np); call.put(o_pl, ln_spl_epl4, 32 * Nl); }
+    if (decide) call.put(o_cov, cov, 4 * C);
+    PLBA_TRY(call.upload());
+    DArr<char> old[6];      // the pools' former blocks: released when the call returns, which is after its wait
     const size_t rows[2] = {Np, Nl};
     for (int k = 0; k < 2; ++k) {
         PLBA_HIPCK(p, grow(st->ids[k], 4 * st->used[k], 4 * (st->used[k] + rows[k]), old[3 * k], s));
         PLBA_HIPCK(p, grow(st->vals[k], 8 * st->used[k], 8 * (st->used[k] + rows[k]), old[3 * k + 1], s));
         PLBA_HIPCK(p, grow(st->meta[k], 8 * (size_t)n0, 8 * ((size_t)n0 + B), old[3 * k + 2], s));
     }
-    auto i32 = [&](size_t o) { return reinterpret_cast<int32_t*>(blk.p + o); };
-    auto f64 = [&](size_t o) { return reinterpret_cast<double*>(blk.p + o); };
     DescendDev t{};
     t.vp = voc_dev(st->voc[0]); t.vl = voc_dev(st->voc[1]);
-    t.desc = reinterpret_cast<const uint4*>(blk.p + o_d); t.Np = (int)Np; t.Nl = (int)Nl; t.word = i32(o_w);
+    t.desc = call.dev<uint4>(o_d); t.Np = (int)Np; t.Nl = (int)Nl; t.word = call.dev<int32_t>(o_w);
     const int longest = std::max(std::max(max_rows(B, ps), max_rows(B, ls)), 1);
     BuildDev bd{};
     bd.B = B; bd.n0 = n0; bd.Np = (int)Np; bd.NP = pow2_at_least(longest);
-    bd.start_p = i32(o_ps); bd.start_l = i32(o_ls); bd.word = t.word; bd.ww_p = t.vp.word_weight; bd.ww_l = t.vl.word_weight;
+    bd.start_p = call.dev<int32_t>(o_ps); bd.start_l = call.dev<int32_t>(o_ls); bd.word = t.word; bd.ww_p = t.vp.word_weight; bd.ww_l = t.vl.word_weight;
     bd.acc_p = bw::accumulates(t.vp.weighting); bd.acc_l = bw::accumulates(t.vl.weighting);
-    bd.out_id = i32(o_id); bd.out_val = f64(o_val); bd.out_nnz = i32(o_nnz);
+    bd.out_id = call.dev<int32_t>(o_id); bd.out_val = call.dev<double>(o_val); bd.out_nnz = call.dev<int32_t>(o_nnz);
     bd.db_id_p = reinterpret_cast<int32_t*>(st->ids[0].p); bd.db_id_l = reinterpret_cast<int32_t*>(st->ids[1].p);
     bd.db_val_p = reinterpret_cast<double*>(st->vals[0].p); bd.db_val_l = reinterpret_cast<double*>(st->vals[1].p);
     bd.meta_p = reinterpret_cast<int2*>(st->meta[0].p); bd.meta_l = reinterpret_cast<int2*>(st->meta[1].p);
     bd.used_p = (int)st->used[0]; bd.used_l = (int)st->used[1];
-    bd.pos_p = want_std ? f64(o_pp) : nullptr; bd.pos_l = want_std ? f64(o_pl) : nullptr; bd.stat = f64(o_stat);
+    bd.pos_p = want_std ? call.dev<double>(o_pp) : nullptr; bd.pos_l = want_std ? call.dev<double>(o_pl) : nullptr; bd.stat = call.dev<double>(o_stat);
     PLBA_HIPCK(p, transform_launch(t, bd, s));
     ScoreDev sc{};
-    sc.B = B; sc.n0 = n0; sc.NQ = longest; sc.live = reinterpret_cast<const uint8_t*>(blk.p + o_live);
+    sc.B = B; sc.n0 = n0; sc.NQ = longest; sc.live = call.dev<uint8_t>(o_live);
     sc.id_p = bd.db_id_p; sc.id_l = bd.db_id_l; sc.val_p = bd.db_val_p; sc.val_l = bd.db_val_l; sc.meta_p = bd.meta_p; sc.meta_l = bd.meta_l;
-    sc.sp = f64(o_sp); sc.sl = f64(o_sl); sc.use_p = use_p; sc.use_l = use_l;
+    sc.sp = call.dev<double>(o_sp); sc.sl = call.dev<double>(o_sl); sc.use_p = use_p; sc.use_l = use_l;
     PLBA_HIPCK(p, ensure_dyn_lds(reinterpret_cast<const void*>(k_bow_score), 12 * bw::MAX_DESC));
     const unsigned chunks = (unsigned)(((size_t)n0 + B + SCORE_CHUNK - 1) / SCORE_CHUNK);
     hipLaunchKernelGGL(k_bow_score, dim3(chunks, 2 * (unsigned)B), dim3(256), 12 * (size_t)sc.NQ, s, sc);
     DecideDev dc{};
     dc.B = B; dc.n0 = n0; dc.mode = opt->mode; dc.topk = opt->topk; dc.lc_kf_dist = opt->lc_kf_dist; dc.lc_kf_max_dist = opt->lc_kf_max_dist;
     dc.lc_nkf_closest = opt->lc_nkf_closest; dc.min_lm_cov_graph = opt->min_lm_cov_graph; dc.min_kf_local_map = opt->min_kf_local_map;
-    dc.live = sc.live; dc.start_p = bd.start_p; dc.start_l = bd.start_l; dc.stat = bd.stat; dc.sp = sc.sp; dc.sl = sc.sl; dc.s = f64(o_s);
-    dc.sf = reinterpret_cast<float*>(blk.p + o_sf); dc.cov = decide ? i32(o_cov) : nullptr; dc.cand_i = i32(o_ci); dc.cand_d = f64(o_cd);
+    dc.live = sc.live; dc.start_p = bd.start_p; dc.start_l = bd.start_l; dc.stat = bd.stat; dc.sp = sc.sp; dc.sl = sc.sl; dc.s = call.dev<double>(o_s);
+    dc.sf = call.dev<float>(o_sf); dc.cov = decide ? call.dev<int32_t>(o_cov) : nullptr; dc.cand_i = call.dev<int32_t>(o_ci); dc.cand_d = call.dev<double>(o_cd);
     hipLaunchKernelGGL(k_bow_decide, dim3((unsigned)B), dim3(256), 0, s, dc);
     PLBA_HIPCK(p, hipGetLastError());
-    PLBA_HIPCK(p, hipMemcpyAsync(sg.down, blk.p + up, down, hipMemcpyDeviceToHost, s));
-    PLBA_HIPCK(p, plba_stream_wait(p, s));      // the call's one blocking wait
+    PLBA_TRY(call.download());
 
-    const char* hd = sg.down;
-    auto dn = [&](size_t o) { return hd + (o - up); };
-    const int32_t* nz = reinterpret_cast<const int32_t*>(dn(o_nnz));
+    const int32_t* nz = call.down<int32_t>(o_nnz);
     st->n = n0 + B; st->n_live += B; st->live.resize((size_t)n0 + B, 1);
     st->used[0] += Np; st->used[1] += Nl;
     for (int b = 0; b < B; ++b) { st->nnz[0] += (size_t)nz[b]; st->nnz[1] += (size_t)nz[B + b]; }
     out->first_index = n0;
-    if (out->score_p) memcpy(out->score_p, dn(o_sp), 8 * R);
-    if (out->score_l) memcpy(out->score_l, dn(o_sl), 8 * R);
-    if (out->score) memcpy(out->score, dn(o_s), 8 * R);
-    if (out->score_f32) memcpy(out->score_f32, dn(o_sf), 4 * R);
+    if (out->score_p) memcpy(out->score_p, call.down<double>(o_sp), 8 * R);
+    if (out->score_l) memcpy(out->score_l, call.down<double>(o_sl), 8 * R);
+    if (out->score) memcpy(out->score, call.down<double>(o_s), 8 * R);
+    if (out->score_f32) memcpy(out->score_f32, call.down<float>(o_sf), 4 * R);
     if (use_p) {
-        if (out->pt_word && Np) memcpy(out->pt_word, dn(o_w), 4 * Np);
-        if (out->pt_bow_id && Np) memcpy(out->pt_bow_id, dn(o_id), 4 * Np);
-        if (out->pt_bow_val && Np) memcpy(out->pt_bow_val, dn(o_val), 8 * Np);
+        if (out->pt_word && Np) memcpy(out->pt_word, call.down<int32_t>(o_w), 4 * Np);
+        if (out->pt_bow_id && Np) memcpy(out->pt_bow_id, call.down<int32_t>(o_id), 4 * Np);
+        if (out->pt_bow_val && Np) memcpy(out->pt_bow_val, call.down<double>(o_val), 8 * Np);
         if (out->pt_nnz) memcpy(out->pt_nnz, nz, 4 * (size_t)B);
     }
     if (use_l) {
-        if (out->ln_word && Nl) memcpy(out->ln_word, dn(o_w) + 4 * Np, 4 * Nl);
-        if (out->ln_bow_id && Nl) memcpy(out->ln_bow_id, dn(o_id) + 4 * Np, 4 * Nl);
-        if (out->ln_bow_val && Nl) memcpy(out->ln_bow_val, dn(o_val) + 8 * Np, 8 * Nl);
+        if (out->ln_word && Nl) memcpy(out->ln_word, call.down<int32_t>(o_w) + Np, 4 * Nl);
+        if (out->ln_bow_id && Nl) memcpy(out->ln_bow_id, call.down<int32_t>(o_id) + Np, 4 * Nl);
+        if (out->ln_bow_val && Nl) memcpy(out->ln_bow_val, call.down<double>(o_val) + Np, 8 * Nl);
         if (out->ln_nnz) memcpy(out->ln_nnz, nz + B, 4 * (size_t)B);
     }
     if (decide) {
-        const int32_t* ci = reinterpret_cast<const int32_t*>(dn(o_ci));
-        const double* cd = reinterpret_cast<const double*>(dn(o_cd));
+        const int32_t* ci = call.down<int32_t>(o_ci);
+        const double* cd = call.down<double>(o_cd);
         for (int b = 0; b < B; ++b) {
             plba_bow_candidate& c = out->cand[b];
             const int32_t* i4 = ci + (size_t)CAND_I * b;

@@ -10,10 +10,9 @@
 // sums only, no order to depend on.  The composed call appends k_loop_gate (one block: the inlier-ratio gate per candidate and the scan
 // of the surviving feature counts over B), k_loop_gather (the matched pairs in ascending i1 into k_relpose's arrays) and k_relpose itself
 // (plba_relpose.hip, through plba_relpose_launch.h).  The arithmetic is plba_match_dev.h, shared with the host check and the drop-in.
-#include <vector>
-
+// The host side of both calls (one block, one copy up, one down, one wait) is plba_batch_call.h's.
+#include "plba_batch_call.h"
 #include "plba_match_dev.h"
-#include "plba_problem.h"
 #include "plba_relpose_launch.h"
 
 namespace plba {
@@ -201,12 +200,6 @@ __global__ __launch_bounds__(256) void k_loop_gather(LoopDev d) {
     }
 }
 
-size_t al16(size_t b) { return (b + 15) & ~(size_t)15; }
-struct Layout {
-    size_t off = 0;
-    size_t take(size_t bytes) { const size_t o = off; off += al16(bytes); return o; }
-};
-
 // (problem, direction, query tile) of every search that resolve() will read: 1 -> 2 wherever both sides have a row (its triples are
 // also nn3), 2 -> 1 only where the mutual rule can keep a match
 void build_work(int P, const int32_t* a_start, const int32_t* b_start, const int32_t* flags, std::vector<int4>& work) {
@@ -221,11 +214,6 @@ void build_work(int P, const int32_t* a_start, const int32_t* b_start, const int
     }
 }
 
-const char* check_starts(int P, const int32_t* st) {
-    if (st[0] != 0) return "a start array does not begin at 0";
-    for (int b = 0; b < P; ++b) if (st[b + 1] < st[b]) return "a start array descends";
-    return nullptr;
-}
 bool nnr_valid(float v) { return std::isfinite(v) && v > 0.0f; }
 
 // the two matching launches
@@ -234,17 +222,6 @@ hipError_t match_launch(const MatchDev& d, size_t n_work, hipStream_t s) {
     hipLaunchKernelGGL(k_match_finish, dim3((unsigned)d.P), dim3(256), 0, s, d);
     return hipGetLastError();
 }
-
-// staging memory of a call: the pinned area when it is there and large enough, pageable stand-ins otherwise
-struct Staged {
-    std::vector<char> h_up, h_down;
-    char *up = nullptr, *down = nullptr;
-    void take(size_t n_up, size_t n_down) {
-        up = (char*)stage_take(n_up); down = (char*)stage_take(n_down);
-        if (!up) { h_up.resize(n_up); up = h_up.data(); }
-        if (!down) { h_down.resize(n_down); down = h_down.data(); }
-    }
-};
 
 }  // namespace
 }  // namespace plba
@@ -277,42 +254,30 @@ int plba_match_descriptors(plba_problem* p, const plba_match_options* opt, int B
     std::vector<int4> work;
     build_work(B, a_start, b_start, flags.data(), work);
     // one device block: [starts | nnr | flags | work | desc1 | desc2 || triples 2 -> 1 || matches | counts | triples 1 -> 2]; the copy up takes
-    // what is before the first bar, the copy down what is behind the second; every section starts on a 16-byte boundary
+    // what is before the first bar, the copy down what is behind the second; the section between them stays on the device
     Layout L;
-    const size_t o_as = L.take(4 * ((size_t)B + 1)), o_bs = L.take(4 * ((size_t)B + 1)), o_nnr = L.take(4 * (size_t)B), o_fl = L.take(4 * (size_t)B),
-                 o_wk = L.take(16 * work.size()), o_dA = L.take(32 * NA), o_dB = L.take(32 * NB), up = L.off, o_nB = L.take(12 * NB), o_down = L.off,
-                 o_m = L.take(4 * NA), o_cnt = L.take(4 * (size_t)B), o_nA = L.take(12 * NA), total = L.off;
-    const size_t down = total - o_down;
-    PLBA_HIPCK(p, hipSetDevice(p->device));
-    hipStream_t s = p->stream;
-    DArrStreamScope staged(s, p->have_ctx ? p->ctx.stage : nullptr);
-    Staged st;
-    st.take(up, down);
-    char* hu = st.up;
-    memcpy(hu + o_as, a_start, 4 * ((size_t)B + 1)); memcpy(hu + o_bs, b_start, 4 * ((size_t)B + 1));
-    for (int b = 0; b < B; ++b) reinterpret_cast<float*>(hu + o_nnr)[b] = nnr_b ? nnr_b[b] : opt->nnr;
-    memcpy(hu + o_fl, flags.data(), 4 * (size_t)B);
-    if (!work.empty()) memcpy(hu + o_wk, work.data(), 16 * work.size());
-    if (NA) memcpy(hu + o_dA, descA32, 32 * NA);
-    if (NB) memcpy(hu + o_dB, descB32, 32 * NB);
-    DArr<char> blk;
-    PLBA_HIPCK(p, blk.alloc(total, false));
-    PLBA_HIPCK(p, hipMemcpyAsync(blk.p, hu, up, hipMemcpyHostToDevice, s));
+    const size_t n_st = 4 * ((size_t)B + 1);
+    const size_t o_as = L.take(n_st), o_bs = L.take(n_st), o_nnr = L.take(4 * (size_t)B), o_fl = L.take(4 * (size_t)B), o_wk = L.take(16 * work.size()),
+                 o_dA = L.take(32 * NA), o_dB = L.take(32 * NB), up_end = L.off, o_nB = L.take(12 * NB), down_begin = L.off, o_m = L.take(4 * NA),
+                 o_cnt = L.take(4 * (size_t)B), o_nA = L.take(12 * NA);
+    BatchCall call(p);
+    PLBA_TRY(call.open(L.off, up_end, down_begin, L.off));
+    call.put(o_as, a_start, n_st); call.put(o_bs, b_start, n_st);
+    for (int b = 0; b < B; ++b) call.up<float>(o_nnr)[b] = nnr_b ? nnr_b[b] : opt->nnr;
+    call.put(o_fl, flags.data(), 4 * (size_t)B); call.put(o_wk, work.data(), 16 * work.size());
+    call.put(o_dA, descA32, 32 * NA); call.put(o_dB, descB32, 32 * NB);
+    PLBA_TRY(call.upload());
     MatchDev d;
     d.P = B;
-    d.a_start = reinterpret_cast<const int32_t*>(blk.p + o_as); d.b_start = reinterpret_cast<const int32_t*>(blk.p + o_bs);
-    d.descA = reinterpret_cast<const uint4*>(blk.p + o_dA); d.descB = reinterpret_cast<const uint4*>(blk.p + o_dB);
-    d.work = reinterpret_cast<const int4*>(blk.p + o_wk); d.nnr = reinterpret_cast<const float*>(blk.p + o_nnr);
-    d.flags = reinterpret_cast<const int32_t*>(blk.p + o_fl);
-    d.nnA = reinterpret_cast<int32_t*>(blk.p + o_nA); d.nnB = reinterpret_cast<int32_t*>(blk.p + o_nB);
-    d.m12 = reinterpret_cast<int32_t*>(blk.p + o_m); d.count = reinterpret_cast<int32_t*>(blk.p + o_cnt);
-    PLBA_HIPCK(p, match_launch(d, work.size(), s));
-    PLBA_HIPCK(p, hipMemcpyAsync(st.down, blk.p + o_down, down, hipMemcpyDeviceToHost, s));
-    PLBA_HIPCK(p, plba_stream_wait(p, s));      // the call's one blocking wait
-    const char* hd = st.down;
-    if (NA) memcpy(matches_12, hd + (o_m - o_down), 4 * NA);
-    memcpy(n_matches, hd + (o_cnt - o_down), 4 * (size_t)B);
-    if (nn3 && NA) memcpy(nn3, hd + (o_nA - o_down), 12 * NA);
+    d.a_start = call.dev<int32_t>(o_as); d.b_start = call.dev<int32_t>(o_bs);
+    d.descA = call.dev<uint4>(o_dA); d.descB = call.dev<uint4>(o_dB);
+    d.work = call.dev<int4>(o_wk); d.nnr = call.dev<float>(o_nnr); d.flags = call.dev<int32_t>(o_fl);
+    d.nnA = call.dev<int32_t>(o_nA); d.nnB = call.dev<int32_t>(o_nB); d.m12 = call.dev<int32_t>(o_m); d.count = call.dev<int32_t>(o_cnt);
+    PLBA_HIPCK(p, match_launch(d, work.size(), call.s));
+    PLBA_TRY(call.download());
+    if (NA) memcpy(matches_12, call.down<int32_t>(o_m), 4 * NA);
+    memcpy(n_matches, call.down<int32_t>(o_cnt), 4 * (size_t)B);
+    if (nn3 && NA) memcpy(nn3, call.down<int32_t>(o_nA), 12 * NA);
     return PLBA_OK;
 }
 
@@ -343,8 +308,7 @@ int plba_verify_loop_candidates(plba_problem* p, const plba_loop_options* opt, i
     if (!nnr_valid(opt->match_pt.nnr) || !nnr_valid(opt->match_ln.nnr)) PLBA_FAIL(p, PLBA_ERR_INVALID, "plba_verify_loop_candidates: nnr is not finite or not positive");
     if (!std::isfinite(opt->lc_inlier_ratio)) PLBA_FAIL(p, PLBA_ERR_INVALID, "plba_verify_loop_candidates: lc_inlier_ratio is not finite");
     if (const char* why = relpose_check_options(opt->relpose, fx, fy, cx, cy)) PLBA_FAIL(p, PLBA_ERR_INVALID, "plba_verify_loop_candidates: %s", why);
-    auto finite = [](const double* a, size_t n) { for (size_t i = 0; i < n; ++i) if (!std::isfinite(a[i])) return false; return true; };
-    if (!finite(P3A, 3 * NpA) || !finite(uvB, 2 * NpB) || !finite(sPeP6A, 6 * NlA) || !finite(l3B, 3 * NlB))
+    if (!all_finite(P3A, 3 * NpA) || !all_finite(uvB, 2 * NpB) || !all_finite(sPeP6A, 6 * NlA) || !all_finite(l3B, 3 * NlB))
         PLBA_FAIL(p, PLBA_ERR_INVALID, "plba_verify_loop_candidates: non-finite input");
 
     // 2B matching problems: the candidates' points, then their lines; rows of desc1 / desc2 likewise
@@ -358,68 +322,53 @@ int plba_verify_loop_candidates(plba_problem* p, const plba_loop_options* opt, i
     std::vector<int4> work;
     build_work(P, as.data(), bs.data(), flags.data(), work);
     // one device block: [starts | nnr | flags | work | desc1 | desc2 | features || triples | k_relpose's starts and arrays || matches | counts | gate |
-    // masks | k_relpose's results]; up: before the first bar, down: behind the second
+    // masks | k_relpose's results]; the copy up takes what is before the first bar, the copy down what is behind the second; the section
+    // between them stays on the device
     Layout L;
-    const size_t o_as = L.take(4 * ((size_t)P + 1)), o_bs = L.take(4 * ((size_t)P + 1)), o_nnr = L.take(4 * (size_t)P), o_fl = L.take(4 * (size_t)P),
-                 o_wk = L.take(16 * work.size()), o_dA = L.take(32 * NA), o_dB = L.take(32 * NB), o_P3 = L.take(24 * NpA), o_uv = L.take(16 * NpB),
-                 o_pq = L.take(48 * NlA), o_l3 = L.take(24 * NlB), up = L.off;
-    const size_t o_nA = L.take(12 * NA), o_nB = L.take(12 * NB), o_rps = L.take(4 * ((size_t)B + 1)), o_rls = L.take(4 * ((size_t)B + 1)), o_gP = L.take(24 * NpA),
-                 o_gu = L.take(16 * NpA), o_gq = L.take(48 * NlA), o_gl = L.take(24 * NlA), o_down = L.off;
+    const size_t n_st = 4 * ((size_t)P + 1), n_rst = 4 * ((size_t)B + 1);
+    const size_t o_as = L.take(n_st), o_bs = L.take(n_st), o_nnr = L.take(4 * (size_t)P), o_fl = L.take(4 * (size_t)P), o_wk = L.take(16 * work.size()),
+                 o_dA = L.take(32 * NA), o_dB = L.take(32 * NB), o_P3 = L.take(24 * NpA), o_uv = L.take(16 * NpB), o_pq = L.take(48 * NlA),
+                 o_l3 = L.take(24 * NlB), up_end = L.off;
+    const size_t o_nA = L.take(12 * NA), o_nB = L.take(12 * NB), o_rps = L.take(n_rst), o_rls = L.take(n_rst), o_gP = L.take(24 * NpA), o_gu = L.take(16 * NpA),
+                 o_gq = L.take(48 * NlA), o_gl = L.take(24 * NlA), down_begin = L.off;
     const size_t o_m = L.take(4 * NA), o_cnt = L.take(4 * (size_t)P), o_gi = L.take(4 * (size_t)B), o_gd = L.take(16 * (size_t)B), o_pm = L.take(NpA),
-                 o_lm = L.take(NlA), o_od = L.take(8 * (size_t)RP_OUT_D * B), o_oi = L.take(4 * (size_t)RP_OUT_I * B), total = L.off;
-    const size_t down = total - o_down;
-    PLBA_HIPCK(p, hipSetDevice(p->device));
-    hipStream_t s = p->stream;
-    DArrStreamScope staged(s, p->have_ctx ? p->ctx.stage : nullptr);
-    Staged st;
-    st.take(up, down);
-    char* hu = st.up;
-    memcpy(hu + o_as, as.data(), 4 * ((size_t)P + 1)); memcpy(hu + o_bs, bs.data(), 4 * ((size_t)P + 1));
-    for (int b = 0; b < B; ++b) { reinterpret_cast<float*>(hu + o_nnr)[b] = opt->match_pt.nnr; reinterpret_cast<float*>(hu + o_nnr)[B + b] = opt->match_ln.nnr; }
-    memcpy(hu + o_fl, flags.data(), 4 * (size_t)P);
-    if (!work.empty()) memcpy(hu + o_wk, work.data(), 16 * work.size());
-    if (NpA) { memcpy(hu + o_dA, descPA32, 32 * NpA); memcpy(hu + o_P3, P3A, 24 * NpA); }
-    if (NlA) { memcpy(hu + o_dA + 32 * NpA, descLA32, 32 * NlA); memcpy(hu + o_pq, sPeP6A, 48 * NlA); }
-    if (NpB) { memcpy(hu + o_dB, descPB32, 32 * NpB); memcpy(hu + o_uv, uvB, 16 * NpB); }
-    if (NlB) { memcpy(hu + o_dB + 32 * NpB, descLB32, 32 * NlB); memcpy(hu + o_l3, l3B, 24 * NlB); }
-    DArr<char> blk;
-    PLBA_HIPCK(p, blk.alloc(total, false));
-    PLBA_HIPCK(p, hipMemcpyAsync(blk.p, hu, up, hipMemcpyHostToDevice, s));
-    auto i32 = [&](size_t o) { return reinterpret_cast<int32_t*>(blk.p + o); };
-    auto f64 = [&](size_t o) { return reinterpret_cast<double*>(blk.p + o); };
+                 o_lm = L.take(NlA), o_od = L.take(8 * (size_t)RP_OUT_D * B), o_oi = L.take(4 * (size_t)RP_OUT_I * B);
+    BatchCall call(p);
+    PLBA_TRY(call.open(L.off, up_end, down_begin, L.off));
+    call.put(o_as, as.data(), n_st); call.put(o_bs, bs.data(), n_st);
+    for (int b = 0; b < B; ++b) { call.up<float>(o_nnr)[b] = opt->match_pt.nnr; call.up<float>(o_nnr)[B + b] = opt->match_ln.nnr; }
+    call.put(o_fl, flags.data(), 4 * (size_t)P); call.put(o_wk, work.data(), 16 * work.size());
+    call.put(o_dA, descPA32, 32 * NpA); call.put(o_dA + 32 * NpA, descLA32, 32 * NlA); call.put(o_P3, P3A, 24 * NpA); call.put(o_pq, sPeP6A, 48 * NlA);
+    call.put(o_dB, descPB32, 32 * NpB); call.put(o_dB + 32 * NpB, descLB32, 32 * NlB); call.put(o_uv, uvB, 16 * NpB); call.put(o_l3, l3B, 24 * NlB);
+    PLBA_TRY(call.upload());
     MatchDev d;
     d.P = P;
-    d.a_start = i32(o_as); d.b_start = i32(o_bs);
-    d.descA = reinterpret_cast<const uint4*>(blk.p + o_dA); d.descB = reinterpret_cast<const uint4*>(blk.p + o_dB);
-    d.work = reinterpret_cast<const int4*>(blk.p + o_wk); d.nnr = reinterpret_cast<const float*>(blk.p + o_nnr); d.flags = i32(o_fl);
-    d.nnA = i32(o_nA); d.nnB = i32(o_nB); d.m12 = i32(o_m); d.count = i32(o_cnt);
-    PLBA_HIPCK(p, match_launch(d, work.size(), s));
+    d.a_start = call.dev<int32_t>(o_as); d.b_start = call.dev<int32_t>(o_bs);
+    d.descA = call.dev<uint4>(o_dA); d.descB = call.dev<uint4>(o_dB);
+    d.work = call.dev<int4>(o_wk); d.nnr = call.dev<float>(o_nnr); d.flags = call.dev<int32_t>(o_fl);
+    d.nnA = call.dev<int32_t>(o_nA); d.nnB = call.dev<int32_t>(o_nB); d.m12 = call.dev<int32_t>(o_m); d.count = call.dev<int32_t>(o_cnt);
+    PLBA_HIPCK(p, match_launch(d, work.size(), call.s));
     LoopDev g;
     g.B = B; g.a_start = d.a_start; g.b_start = d.b_start; g.m12 = d.m12; g.count = d.count;
     g.use_points = opt->use_points ? 1 : 0; g.use_lines = opt->use_lines ? 1 : 0; g.lc_inlier_ratio = opt->lc_inlier_ratio;
-    g.gate_i = i32(o_gi); g.gate_d = f64(o_gd); g.rp_ps = i32(o_rps); g.rp_ls = i32(o_rls);
-    g.P3A = f64(o_P3); g.uvB = f64(o_uv); g.pq6A = f64(o_pq); g.l3B = f64(o_l3); g.NpA = (int)NpA; g.NpB = (int)NpB;
-    g.gP3 = f64(o_gP); g.guv = f64(o_gu); g.gpq = f64(o_gq); g.gl3 = f64(o_gl);
-    g.pm = reinterpret_cast<uint8_t*>(blk.p + o_pm); g.lm = reinterpret_cast<uint8_t*>(blk.p + o_lm);
-    hipLaunchKernelGGL(k_loop_gate, dim3(1), dim3(256), 0, s, g);
-    hipLaunchKernelGGL(k_loop_gather, dim3((unsigned)P), dim3(256), 0, s, g);
+    g.gate_i = call.dev<int32_t>(o_gi); g.gate_d = call.dev<double>(o_gd); g.rp_ps = call.dev<int32_t>(o_rps); g.rp_ls = call.dev<int32_t>(o_rls);
+    g.P3A = call.dev<double>(o_P3); g.uvB = call.dev<double>(o_uv); g.pq6A = call.dev<double>(o_pq); g.l3B = call.dev<double>(o_l3);
+    g.NpA = (int)NpA; g.NpB = (int)NpB;
+    g.gP3 = call.dev<double>(o_gP); g.guv = call.dev<double>(o_gu); g.gpq = call.dev<double>(o_gq); g.gl3 = call.dev<double>(o_gl);
+    g.pm = call.dev<uint8_t>(o_pm); g.lm = call.dev<uint8_t>(o_lm);
+    hipLaunchKernelGGL(k_loop_gate, dim3(1), dim3(256), 0, call.s, g);
+    hipLaunchKernelGGL(k_loop_gather, dim3((unsigned)P), dim3(256), 0, call.s, g);
     PLBA_HIPCK(p, hipGetLastError());
     RelposeDev r;
     relpose_set_options(opt->relpose, fx, fy, cx, cy, r.o);
     r.pt_start = g.rp_ps; r.ln_start = g.rp_ls; r.P3 = g.gP3; r.uv2 = g.guv; r.pq6 = g.gpq; r.l3 = g.gl3; r.T0 = nullptr;
-    r.pt_in = g.pm; r.ln_in = g.lm; r.out_d = f64(o_od); r.out_i = i32(o_oi);
-    PLBA_HIPCK(p, relpose_launch(r, B, s));
-    PLBA_HIPCK(p, hipMemcpyAsync(st.down, blk.p + o_down, down, hipMemcpyDeviceToHost, s));
-    PLBA_HIPCK(p, plba_stream_wait(p, s));      // the call's one blocking wait
+    r.pt_in = g.pm; r.ln_in = g.lm; r.out_d = call.dev<double>(o_od); r.out_i = call.dev<int32_t>(o_oi);
+    PLBA_HIPCK(p, relpose_launch(r, B, call.s));
+    PLBA_TRY(call.download());
 
-    const char* hd = st.down;
-    const int32_t* m12 = reinterpret_cast<const int32_t*>(hd + (o_m - o_down));
-    const int32_t* cnt = reinterpret_cast<const int32_t*>(hd + (o_cnt - o_down));
-    const int32_t* gi = reinterpret_cast<const int32_t*>(hd + (o_gi - o_down));
-    const double* gd = reinterpret_cast<const double*>(hd + (o_gd - o_down));
-    const uint8_t *pm = reinterpret_cast<const uint8_t*>(hd + (o_pm - o_down)), *lm = reinterpret_cast<const uint8_t*>(hd + (o_lm - o_down));
-    const double* od = reinterpret_cast<const double*>(hd + (o_od - o_down));
-    const int32_t* oi = reinterpret_cast<const int32_t*>(hd + (o_oi - o_down));
+    const int32_t *m12 = call.down<int32_t>(o_m), *cnt = call.down<int32_t>(o_cnt), *gi = call.down<int32_t>(o_gi), *oi = call.down<int32_t>(o_oi);
+    const double *gd = call.down<double>(o_gd), *od = call.down<double>(o_od);
+    const uint8_t *pm = call.down<uint8_t>(o_pm), *lm = call.down<uint8_t>(o_lm);
     if (NpA) memcpy(pt_match, m12, 4 * NpA);
     if (NlA) memcpy(ln_match, m12 + NpA, 4 * NlA);
     size_t kp = 0, kl = 0;      // where a candidate's pairs begin in k_relpose's arrays: the device's scan, repeated
