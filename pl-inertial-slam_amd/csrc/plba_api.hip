@@ -379,30 +379,24 @@ int plba_set_shard(plba_problem* p, int rank, int world, plba_allreduce_fn fn, v
 int plba_dense_solve(plba_problem* p, int n, const double* A, const double* b, double* x, int* ok) {
     if (!p || n <= 0 || !A || !b || !x) return PLBA_ERR_INVALID;
     HIPCK(p, hipSetDevice(p->device));
-    const int Ppad = std::max(TILE, (n + TILE - 1) / TILE * TILE), ld = Ppad;
-    const size_t sysn = (size_t)(Ppad + TILE) * ld;
-    std::vector<double> h(sysn, 0.0);
+    const int Ppad = dense_ppad(n), ld = Ppad;
+    std::vector<double> h(dense_counts(Ppad, ld).sys_len, 0.0);
     for (int r = 0; r < n; ++r) memcpy(&h[(size_t)r * ld], A + (size_t)r * n, (size_t)n * 8);
     for (int r = n; r < Ppad; ++r) h[(size_t)r * ld + r] = 1.0;
     memcpy(&h[(size_t)Ppad * ld], b, (size_t)n * 8);
-    DArr<double> sys, Lfac, xx, Linv, LT32, rd32, Ninv;
-    DArr<Ctrl> ctrl;
-    DArr<int> flags, cflags;
+    DArr<double> sys;
+    DArr<Ctrl> ctrl; DenseWork work;
     DArrStreamScope staged(p->stream, p->have_ctx ? p->ctx.stage : nullptr);      // `h` stays alive until the final wait below
-    HIPCK(p, sys.upload(h)); HIPCK(p, Lfac.alloc(sysn)); HIPCK(p, xx.alloc(ld)); HIPCK(p, ctrl.alloc(1));
-    HIPCK(p, Linv.alloc((size_t)(Ppad / TILE) * TILE * TILE)); HIPCK(p, flags.alloc(Ppad / TILE));
-    HIPCK(p, LT32.alloc((size_t)Ppad * 64)); HIPCK(p, rd32.alloc(Ppad));
-    HIPCK(p, cflags.alloc((size_t)(Ppad / 32 + 2) * (Ppad / 32)));
+    HIPCK(p, sys.upload(h)); HIPCK(p, ctrl.alloc(1)); HIPCK(p, work.alloc(Ppad, ld, ninv_fits(Ppad)));
     Ctrl c0; memset(&c0, 0, sizeof c0); c0.solver_ok = 1;
     HIPCK(p, plba_h2d(p, ctrl.p, &c0, sizeof c0));
     DevBuf d; memset(&d, 0, sizeof d);
-    d.P = n; d.Ppad = Ppad; d.ld = ld; d.sys = sys.p; d.Lfac = Lfac.p; d.x = xx.p; d.ctrl = ctrl.p; d.Linv = Linv.p; d.flow_flags = flags.p; d.LTblk = LT32.p; d.Linv32 = LT32.p; d.rdblk = rd32.p; d.fb = (p->opt.factor_block == 64) ? 64 : 32; d.chol_flags = cflags.p; d.flow = p->opt.factor_flow != 0; d.wide = p->opt.wide_steps != 0 && !d.flow;
-    if (Ppad / 32 <= NINV_MAX_T) { HIPCK(p, Ninv.alloc((size_t)2 * Ppad * ld)); d.Ninv = Ninv.p; d.Nwork = Ninv.p + (size_t)Ppad * ld; }
+    d.P = n; d.Ppad = Ppad; d.ld = ld; d.sys = sys.p; d.ctrl = ctrl.p; work.bind(d, p->opt);
     launch_cholesky(d, p->opt.use_mfma != 0, 1, p->stream);
     launch_trsv_back(d, p->opt.use_mfma != 0, 1, p->stream);
     HIPCK(p, plba_stream_wait(p, p->stream));
     HIPCK(p, hipGetLastError());
-    HIPCK(p, plba_d2h(p, x, xx.p, (size_t)n * 8));
+    HIPCK(p, plba_d2h(p, x, work.x.p, (size_t)n * 8));
     HIPCK(p, plba_d2h(p, &c0, ctrl.p, sizeof c0));
     if (ok) *ok = c0.solver_ok;
     return PLBA_OK;
@@ -886,7 +880,7 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
         }
     }
     p->P = off;
-    p->Ppad = std::max(TILE, (off + TILE - 1) / TILE * TILE);
+    p->Ppad = dense_ppad(off);
     p->ld = p->Ppad;
     // ---- unified landmark slots / observation arrays ----------------------------------------------------
     if (!p->ctx.lm_host) p->ctx.lm_host = new LmHost;      // (stays with the cached context)
@@ -1151,11 +1145,7 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
     HIPCK(p, p->d_pr_err.alloc(p->pr_n)); HIPCK(p, p->d_pr_dx.alloc(p->pr_n)); HIPCK(p, p->d_pr_chi.alloc(1));
     HIPCK(p, p->d_Hconst.alloc((size_t)p->Ppad * p->ld)); HIPCK(p, p->d_Himu.alloc((size_t)p->Ppad * p->ld)); HIPCK(p, p->d_Himu2.alloc((size_t)p->Ppad * p->ld)); HIPCK(p, p->d_bimu2.alloc(p->ld));
     HIPCK(p, p->d_bprior.alloc(p->ld)); HIPCK(p, p->d_bprior2.alloc(p->ld));
-    HIPCK(p, p->d_bimu.alloc(p->ld)); HIPCK(p, p->d_sys.alloc(sysn)); HIPCK(p, p->d_Lfac.alloc(sysn));
-    HIPCK(p, p->d_bpg.alloc(p->ld)); HIPCK(p, p->d_x.alloc(p->ld));
-    HIPCK(p, p->d_Linv.alloc((size_t)(p->Ppad / TILE) * TILE * TILE)); HIPCK(p, p->d_flow_flags.alloc(p->Ppad / TILE)); p->flow_epoch = 0;
-    HIPCK(p, p->d_chol_flags.alloc((size_t)(p->Ppad / 32 + 2) * (p->Ppad / 32)));
-    HIPCK(p, p->d_LT32.alloc((size_t)p->Ppad * 64)); HIPCK(p, p->d_rd32.alloc(p->Ppad));
+    HIPCK(p, p->d_bimu.alloc(p->ld)); HIPCK(p, p->d_sys.alloc(sysn)); HIPCK(p, p->d_bpg.alloc(p->ld)); HIPCK(p, p->work.alloc(p->Ppad, p->ld, false)); p->flow_epoch = 0;      // (the explicit inverse: below, once the solver's path is known)
     const size_t ngrp = LH.grp.size();      // the fused passes leave one partial per landmark group in the same arrays
     HIPCK(p, p->d_chi_part.alloc(std::max((size_t)(E + 255) / 256, ngrp) + 1)); HIPCK(p, p->d_scale_part.alloc(std::max((size_t)(L + 31) / 32 + 32, ngrp) + 1));      // one partial per landmark workgroup (32 landmarks, plba_kernels.hip LML)
     HIPCK(p, p->d_maxd_part.alloc(std::max((size_t)(L + 31) / 32 + 32, ngrp) + 1)); HIPCK(p, p->d_kfdiag.alloc((size_t)K * 6)); HIPCK(p, p->d_posediag.alloc(p->ld));
@@ -1190,8 +1180,7 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
     d.pr_x0off = p->d_pr_x0off.p; d.pr_off = p->d_pr_off.p; d.pr_x0 = p->d_pr_x0.p; d.pr_J0 = p->d_pr_J0.p; d.pr_r0 = p->d_pr_r0.p;
     if (pr_dev) { d.pr_x0 = pr_dev; d.pr_J0 = pr_dev + pr_nx; d.pr_r0 = pr_dev + pr_nx + (size_t)p->pr_n * p->pr_n; }
     d.pr_err = p->d_pr_err.p; d.pr_dx = p->d_pr_dx.p; d.pr_chi = p->d_pr_chi.p;
-    d.Hconst = p->d_Hconst.p; d.Himu = p->d_Himu.p; d.bimu = p->d_bimu.p; d.Himu_alt = p->d_Himu2.p; d.bimu_alt = p->d_bimu2.p; d.bprior = p->d_bprior.p; d.bprior_alt = p->d_bprior2.p; d.sys = p->d_sys.p; d.Lfac = p->d_Lfac.p; d.bpg = p->d_bpg.p; d.x = p->d_x.p;
-    d.Linv = p->d_Linv.p; d.flow_flags = p->d_flow_flags.p; d.LTblk = p->d_LT32.p; d.Linv32 = p->d_LT32.p; d.rdblk = p->d_rd32.p; d.fb = (p->opt.factor_block == 64) ? 64 : 32; d.chol_flags = p->d_chol_flags.p; d.flow = p->opt.factor_flow != 0; d.wide = p->opt.wide_steps != 0 && !d.flow;
+    d.Hconst = p->d_Hconst.p; d.Himu = p->d_Himu.p; d.bimu = p->d_bimu.p; d.Himu_alt = p->d_Himu2.p; d.bimu_alt = p->d_bimu2.p; d.bprior = p->d_bprior.p; d.bprior_alt = p->d_bprior2.p; d.sys = p->d_sys.p; d.bpg = p->d_bpg.p; p->work.bind(d, p->opt);
     d.chi_part = p->d_chi_part.p; d.scale_part = p->d_scale_part.p; d.maxd_part = p->d_maxd_part.p; d.kfdiag = p->d_kfdiag.p; d.posediag = p->d_posediag.p;
     d.ctrl = p->d_ctrl.p; d.trace = p->d_trace.p; d.trace_cap = TRACE_CAP; d.trace_n = p->d_trace_n.p;
     // ---- structure cache: is this window's pose structure the previous one's? (plba_problem.h, StructCache) ---------------------------------
@@ -1224,8 +1213,7 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
         if (p->chain_ok) {      // the dense system's view: this window's arrays, the cached structure's fields
             DevBuf& dd = p->dd; const DevBuf& o = p->sc.dd;
             dd = d;
-            dd.P = o.P; dd.Ppad = o.Ppad; dd.ld = o.ld; dd.sys = o.sys; dd.Lfac = o.Lfac; dd.x = o.x; dd.Linv = o.Linv; dd.LTblk = o.LTblk; dd.Linv32 = o.Linv32; dd.rdblk = o.rdblk;
-            dd.flow_flags = o.flow_flags; dd.chol_flags = o.chol_flags; dd.Ninv = o.Ninv; dd.Nwork = o.Nwork; dd.dbgbuf = d.dbgbuf;
+            dd.P = o.P; dd.Ppad = o.Ppad; dd.ld = o.ld; dd.sys = o.sys; dd.dbgbuf = d.dbgbuf; p->dwork.bind(dd, p->opt);      // the kept workspace (the options are part of the key)
             dd.band = o.band; dd.twin_m0 = o.twin_m0; dd.twin_fac = o.twin_fac; dd.cs_order = o.cs_order; dd.perm = o.perm; dd.xmap = o.xmap; dd.alt = o.alt; dd.alt2 = o.alt2; dd.wtw = o.wtw;
         }
         p->flow_epoch = 0;
@@ -1437,19 +1425,14 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
                 p->d_W.release();      // must come back zero: the kernels only ever write inside each segment's window
                 HIPCK(p, p->d_W.alloc((size_t)(nel * 9 + 4) * cv.Wld)); HIPCK(p, p->d_Ldinv.alloc((size_t)nel * 81)); HIPCK(p, p->d_Lsub.alloc((size_t)nel * 81));
                 const size_t sysn_d = (size_t)(cv.Pdpad + TILE) * cv.Pdpad;
-                HIPCK(p, p->d_sysd.alloc(sysn_d)); HIPCK(p, p->d_Lfacd.alloc(sysn_d)); HIPCK(p, p->d_xd.alloc(cv.Pdpad));
-                HIPCK(p, p->d_Linvd.alloc((size_t)((cv.Pdpad + TILE - 1) / TILE) * TILE * TILE)); HIPCK(p, p->d_LT32d.alloc((size_t)cv.Pdpad * 64)); HIPCK(p, p->d_rd32d.alloc(cv.Pdpad));
-                HIPCK(p, p->d_flow_flagsd.alloc((cv.Pdpad + TILE - 1) / TILE)); HIPCK(p, p->d_chol_flagsd.alloc((size_t)(cv.Pdpad / 32 + 2) * (cv.Pdpad / 32)));
+                HIPCK(p, p->d_sysd.alloc(sysn_d)); HIPCK(p, p->dwork.alloc(cv.Pdpad, cv.Pdpad, ninv_fits(cv.Pdpad)));
                 cv.cidx = p->d_cidx.p; cv.epos = p->d_epos.p; cv.seg_start = p->d_seg_start.p; cv.seg_col = p->d_seg_col.p;
                 cv.pidx = p->d_pidx.p; cv.ppos = p->d_ppos.p; cv.pslot = p->d_pslot.p; cv.slotcol = p->d_slotcol.p;
                 cv.W = p->d_W.p; cv.Ldinv = p->d_Ldinv.p; cv.Lsub = p->d_Lsub.p;
                 DevBuf& dd = p->dd;
                 dd = d;
                 dd.P = cv.Pd; dd.Ppad = cv.Pdpad; dd.ld = cv.Pdpad;
-                dd.sys = p->d_sysd.p; dd.Lfac = p->d_Lfacd.p; dd.x = p->d_xd.p; dd.Linv = p->d_Linvd.p; dd.LTblk = p->d_LT32d.p; dd.Linv32 = p->d_LT32d.p;
-                dd.rdblk = p->d_rd32d.p; dd.flow_flags = p->d_flow_flagsd.p; dd.chol_flags = p->d_chol_flagsd.p;
-                dd.Ninv = nullptr; dd.Nwork = nullptr;
-                if (cv.Pdpad / 32 <= NINV_MAX_T) { HIPCK(p, p->d_Ninvd.alloc((size_t)2 * cv.Pdpad * cv.Pdpad)); dd.Ninv = p->d_Ninvd.p; dd.Nwork = dd.Ninv + (size_t)cv.Pdpad * cv.Pdpad; }
+                dd.sys = p->d_sysd.p; p->dwork.bind(dd, p->opt);
                 p->chain_ok = true;
             }
         }
@@ -1457,7 +1440,7 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
     lap("chain maps + buffers");
     d.Ninv = nullptr; d.Nwork = nullptr;
     HIPCK(p, p->d_dbgbuf.alloc(128)); d.dbgbuf = p->d_dbgbuf.p; p->dd.dbgbuf = d.dbgbuf;
-    if (!p->chain_ok && p->P > 0 && p->Ppad / 32 <= NINV_MAX_T) { HIPCK(p, p->d_Ninv.alloc((size_t)2 * p->Ppad * p->ld)); d.Ninv = p->d_Ninv.p; d.Nwork = d.Ninv + (size_t)p->Ppad * p->ld; }
+    if (!p->chain_ok && p->P > 0 && ninv_fits(p->Ppad)) { HIPCK(p, p->work.alloc_ninv(p->Ppad, p->ld)); p->work.bind_ninv(d); }
     // ---- structural assembly list (assemble_part): with the chain elimination on, sys is written by the assembly pass and
     // by k_schur_pairs only, so the entries neither of them can make non-zero never need touching again
     d.alist = nullptr; d.nalist = 0;
@@ -1687,7 +1670,7 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
                 p->band_ok = true;
                 p->dd.band = 1;
             } else if (twin_pref && hbt >= 1) {
-                if (!p->dd.Ninv) { HIPCK(p, p->d_Ninvd.alloc((size_t)2 * cv.Pdpad * cv.Pdpad)); p->dd.Ninv = p->d_Ninvd.p; p->dd.Nwork = p->dd.Ninv + (size_t)cv.Pdpad * cv.Pdpad; }
+                if (!p->dd.Ninv) { HIPCK(p, p->dwork.alloc_ninv(cv.Pdpad, cv.Pdpad)); p->dwork.bind_ninv(p->dd); }      // (the multi-chain form keeps the inverse at any length)
                 TwinPlan pl;      // (plba_twin_plan.h: chains and separators, the permutation, the tile list of every launch, k_chain_schur's order)
                 if (twin_plan_build(T, hbt, pl)) {
                     HIPCK(p, p->d_twin_list.upload(pl.list)); HIPCK(p, p->d_twin_perm.upload(pl.perm)); HIPCK(p, p->d_twin_xmap.upload(pl.xmap)); HIPCK(p, p->d_twin_fac.upload(pl.fac));
@@ -1730,7 +1713,7 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
     if (ptime) fprintf(stderr, "[prepare] %zu small buffers in the batch blocks: %.0f KB cleared, %.0f KB copied\n", p->batch.n_batched, p->batch.zused / 1024.0, p->batch.uused / 1024.0);
     // buffers this window did not re-create must not keep a pointer into the batch blocks, which now hold other buffers (the
     // failure class of the re-used-handle fault of round 4): the conditionally allocated ones are dropped when their stamp is old
-    p->d_imu_loc.expire(); p->d_ob_err.expire(); p->d_Ninvd.expire(); p->d_Ninv.expire(); p->d_pr_H.expire();
+    p->d_imu_loc.expire(); p->d_ob_err.expire(); p->work.expire(); p->dwork.expire(); p->d_pr_H.expire();
     p->d_lm_grp.expire(); p->d_lmg_slot.expire(); p->d_lmg_ob0.expire(); p->d_lmg_orig.expire(); p->d_lmg_blk_ij.expire();
     p->d_lmg_blk_start.expire(); p->d_lmg_blk_src.expire(); p->d_lmg_row_kf.expire(); p->d_lmg_row_start.expire(); p->d_lmg_row_src.expire();
     p->d_alist2.expire(); p->d_lmg_ws8.expire(); p->d_lmg_fixed.expire(); p->d_lmg_level.expire(); p->d_col_gather.expire();
@@ -1739,8 +1722,7 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
     p->d_xlist.expire(); p->d_alist.expire(); p->d_trow.expire(); p->d_bkf.expire(); p->d_esrc.expire();
     p->d_cidx.expire(); p->d_epos.expire(); p->d_seg_start.expire(); p->d_seg_col.expire(); p->d_pidx.expire(); p->d_ppos.expire();
     p->d_pslot.expire(); p->d_slotcol.expire(); p->d_kfpos.expire(); p->d_ekf.expire(); p->d_ukf.expire();
-    p->d_Ldinv.expire(); p->d_Lsub.expire(); p->d_xd.expire(); p->d_Linvd.expire(); p->d_rd32d.expire(); p->d_flow_flagsd.expire(); p->d_chol_flagsd.expire();
-    p->d_band_y.expire(); p->d_band_mid.expire();
+    p->d_Ldinv.expire(); p->d_Lsub.expire(); p->d_band_y.expire(); p->d_band_mid.expire();
     p->cur = 0;
     p->saved_valid = true;
     p->dirty = false;
@@ -2016,19 +1998,11 @@ int plba_optimize(plba_problem* p, int max_iters, const volatile uint8_t* abort_
                 } else launch_decide_n(d, lp, p->d_red.p, p->lv.ngrp, p->d_mail, seq, s);
                 MARK(p, 10);
                 if (p->opt.profile >= 2) HIPCK(p, plba_stream_wait(p, s));
-                else {
-                    long spins = 0;
-                    while (__atomic_load_n(&p->h_mail->seq, __ATOMIC_ACQUIRE) != seq) {
-                        if (++spins > (1L << 22)) { HIPCK(p, plba_stream_wait(p, s)); break; }
-                    }
-                }
+                else HIPCK(p, mail_wait(p, s, seq));
             } else {
                 launch_lm_trial(ds, p->lv, p->cur, trial, jac_trial, p->rob, &p->cv, p->dd.x, lm_back_target(p), true, &df, s);      // the trial's IMU / prior edges (linearised into the idle accumulators) | landmark groups; + the decision
                 if (jac_trial) { if ((rc = lm_enqueue_system(p, ds, trial, true))) return rc; spec = true; }      // gated on the device-side decision
-                long spins = 0;
-                while (__atomic_load_n(&p->h_mail->seq, __ATOMIC_ACQUIRE) != seq) {
-                    if (++spins > (1L << 22)) { HIPCK(p, plba_stream_wait(p, s)); break; }
-                }
+                HIPCK(p, mail_wait(p, s, seq));
             }
             if (__atomic_load_n(&p->h_mail->seq, __ATOMIC_ACQUIRE) != seq) FAIL(p, PLBA_ERR_DEVICE, "LM control block was not delivered by the device");
             *p->h_ctrl = p->h_mail->c;
@@ -2120,16 +2094,7 @@ int plba_optimize(plba_problem* p, int max_iters, const volatile uint8_t* abort_
             }
             if (p->opt.profile >= 2) {
                 HIPCK(p, plba_stream_wait(p, s));        // every phase event must have completed before it is read
-            } else {
-                // k_decide is the last kernel of the trial and writes the control block into mapped host memory
-                long spins = 0;
-                while (__atomic_load_n(&p->h_mail->seq, __ATOMIC_ACQUIRE) != seq) {
-                    if (++spins > (1L << 22)) {           // ~ tens of ms: fall back to a real synchronisation (and surface any device error)
-                        HIPCK(p, plba_stream_wait(p, s));
-                        break;
-                    }
-                }
-            }
+            } else HIPCK(p, mail_wait(p, s, seq));      // k_decide is the last kernel of the trial and writes the control block into mapped host memory
             if (__atomic_load_n(&p->h_mail->seq, __ATOMIC_ACQUIRE) != seq) FAIL(p, PLBA_ERR_DEVICE, "LM control block was not delivered by the device");
             *p->h_ctrl = p->h_mail->c;
             if ((int)p->trace.size() < TRACE_CAP) p->trace.push_back(p->h_mail->row);      // the trace is kept from the mailbox: no read-back at the end of the call

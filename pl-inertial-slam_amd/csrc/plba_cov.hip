@@ -337,7 +337,7 @@ int cov_run(plba_problem* p, plba_marginals* m) {
     const int K = p->win.K, Np = p->win.Np, Nl = p->win.Nl, L = p->L, E = p->E, P = p->P;
     const bool want_kf = m->want & 1, want_pair = (m->want & 2) && m->n_pairs > 0, want_pt = m->want & 4, want_ln = m->want & 8;
     const int npairs = want_pair ? m->n_pairs : 0;
-    const int Pp = std::max(TILE, (P + TILE - 1) / TILE * TILE), T = Pp / CB;      // (the dense factorisation's padding; ld = Pp)
+    const int Pp = dense_ppad(P), T = Pp / CB;      // (the dense factorisation's padding; ld = Pp)
     // host: the pose blocks the landmarks couple, and their observation pairs in a fixed order (landmark, then observation order)
     std::map<int64_t, std::vector<int32_t>> bl;
     std::vector<std::pair<int, int>> ob;      // (edge, pose offset) of one landmark's observations from free keyframes
@@ -368,19 +368,17 @@ int cov_run(plba_problem* p, plba_marginals* m) {
     }
     const int nblk = (int)(blk.size() / 4);
     const size_t n_out = 1 + (want_kf ? (size_t)K * 225 : 0) + (size_t)npairs * 225 + (size_t)Np * 9 + (size_t)Nl * 36 + (size_t)L;
-    DArr<double> Hp, bp, ierr, ichi, perr, pdx, pchi, bpr, S, Lfac, Linv, LT32, rd32, Ninv, d0, Sig, rec, lmrec, out;
+    DArr<double> Hp, bp, ierr, ichi, perr, pdx, pchi, bpr, S, d0, Sig, rec, lmrec, out;
     DArr<Ctrl> ctrl;
-    DArr<int32_t> dblk, dent, dpairs, stat, fail, flags, cflags;
+    DArr<int32_t> dblk, dent, dpairs, stat, fail; DenseWork work;
     PLBA_HIPCK(p, Hp.alloc((size_t)p->Ppad * p->ld, false)); PLBA_HIPCK(p, bp.alloc(p->ld, false));
     PLBA_HIPCK(p, ierr.alloc((size_t)std::max(p->win.M, 1) * 16, false)); PLBA_HIPCK(p, ichi.alloc((size_t)std::max(p->win.M, 1) * 4, false));
     PLBA_HIPCK(p, perr.alloc(std::max(p->pr_n, 1), false)); PLBA_HIPCK(p, pdx.alloc(std::max(p->pr_n, 1), false));
     PLBA_HIPCK(p, pchi.alloc(4, false)); PLBA_HIPCK(p, bpr.alloc(p->ld, false));
     // the dense factorisation's buffers, as plba_dense_solve sizes them, the explicit inverse at full size whatever path the problem's own
     // solve takes (chain / band / twin problems keep none, or one of the compact system only)
-    const size_t sysn = (size_t)(Pp + TILE) * Pp;
-    PLBA_HIPCK(p, S.alloc(sysn, false)); PLBA_HIPCK(p, Lfac.alloc(sysn, false)); PLBA_HIPCK(p, Ninv.alloc((size_t)2 * Pp * Pp, false));
-    PLBA_HIPCK(p, Linv.alloc((size_t)(Pp / TILE) * TILE * TILE, false)); PLBA_HIPCK(p, LT32.alloc((size_t)Pp * 64, false)); PLBA_HIPCK(p, rd32.alloc(Pp, false));
-    PLBA_HIPCK(p, flags.alloc(Pp / TILE, false)); PLBA_HIPCK(p, cflags.alloc((size_t)(Pp / 32 + 2) * (Pp / 32), false)); PLBA_HIPCK(p, ctrl.alloc(1, false));
+    const DenseCounts wn = dense_counts(Pp, Pp); const size_t sysn = wn.sys_len;
+    PLBA_HIPCK(p, S.alloc(sysn, false)); PLBA_HIPCK(p, work.alloc(Pp, Pp, true, false)); PLBA_HIPCK(p, ctrl.alloc(1, false));      // (cleared below, on the call's stream)
     PLBA_HIPCK(p, d0.alloc(Pp, false)); PLBA_HIPCK(p, Sig.alloc((size_t)Pp * Pp, false));
     PLBA_HIPCK(p, rec.alloc((size_t)std::max(E, 1) * REC, false)); PLBA_HIPCK(p, lmrec.alloc((size_t)std::max(L, 1) * LMREC, false));
     PLBA_HIPCK(p, stat.alloc(std::max(L, 1), false)); PLBA_HIPCK(p, fail.alloc(1, false)); PLBA_HIPCK(p, out.alloc(n_out, false));
@@ -392,10 +390,10 @@ int cov_run(plba_problem* p, plba_marginals* m) {
     PLBA_HIPCK(p, hipMemsetAsync(fail.p, 0xff, 4, s));
     PLBA_HIPCK(p, hipMemsetAsync(Hp.p, 0, (size_t)p->Ppad * p->ld * 8, s));
     PLBA_HIPCK(p, hipMemsetAsync(bp.p, 0, (size_t)p->ld * 8, s));
-    PLBA_HIPCK(p, hipMemsetAsync(S.p, 0, sysn * 8, s)); PLBA_HIPCK(p, hipMemsetAsync(Lfac.p, 0, sysn * 8, s));
-    PLBA_HIPCK(p, hipMemsetAsync(Ninv.p, 0, (size_t)2 * Pp * Pp * 8, s)); PLBA_HIPCK(p, hipMemsetAsync(Linv.p, 0, (size_t)(Pp / TILE) * TILE * TILE * 8, s));
-    PLBA_HIPCK(p, hipMemsetAsync(LT32.p, 0, (size_t)Pp * 64 * 8, s)); PLBA_HIPCK(p, hipMemsetAsync(rd32.p, 0, (size_t)Pp * 8, s));
-    PLBA_HIPCK(p, hipMemsetAsync(flags.p, 0, (size_t)(Pp / TILE) * 4, s)); PLBA_HIPCK(p, hipMemsetAsync(cflags.p, 0, (size_t)(Pp / 32 + 2) * (Pp / 32) * 4, s));
+    PLBA_HIPCK(p, hipMemsetAsync(S.p, 0, sysn * 8, s)); PLBA_HIPCK(p, hipMemsetAsync(work.Lfac.p, 0, sysn * 8, s));
+    PLBA_HIPCK(p, hipMemsetAsync(work.Ninv.p, 0, wn.ninv * 8, s)); PLBA_HIPCK(p, hipMemsetAsync(work.Linv.p, 0, wn.Linv * 8, s));
+    PLBA_HIPCK(p, hipMemsetAsync(work.LT32.p, 0, wn.LT32 * 8, s)); PLBA_HIPCK(p, hipMemsetAsync(work.rd32.p, 0, wn.rd32 * 8, s));
+    PLBA_HIPCK(p, hipMemsetAsync(work.flow_flags.p, 0, wn.flow_flags * 4, s)); PLBA_HIPCK(p, hipMemsetAsync(work.chol_flags.p, 0, wn.chol_flags * 4, s));
     PLBA_HIPCK(p, hipMemsetAsync(ctrl.p, 0, sizeof(Ctrl), s));
     PLBA_HIPCK(p, hipMemsetAsync(&ctrl.p->solver_ok, 1, 1, s));      // solver_ok = 1 (the low byte of a zeroed int)
     // 1. IMU / prior edges at the current estimate into the scratch accumulator (the problem's own accumulators stay as they are)
@@ -420,13 +418,12 @@ int cov_run(plba_problem* p, plba_marginals* m) {
     };
     if (dump) PLBA_HIPCK(p, keep(S.p, p->cov_dbg_S));
     DevBuf dd; memset(&dd, 0, sizeof dd);
-    dd.P = P; dd.Ppad = Pp; dd.ld = Pp; dd.sys = S.p; dd.Lfac = Lfac.p; dd.ctrl = ctrl.p; dd.Linv = Linv.p; dd.flow_flags = flags.p;
-    dd.LTblk = LT32.p; dd.Linv32 = LT32.p; dd.rdblk = rd32.p; dd.fb = 32; dd.chol_flags = cflags.p; dd.flow = 0; dd.wide = 0;
-    dd.Ninv = Ninv.p; dd.Nwork = Ninv.p + (size_t)Pp * Pp;
+    dd.P = P; dd.Ppad = Pp; dd.ld = Pp; dd.sys = S.p; dd.ctrl = ctrl.p;
+    work.bind(dd, p->opt); dd.fb = 32; dd.flow = 0; dd.wide = 0;      // always the multi-launch factorisation in 32-column steps, whatever the problem's options say
     launch_cholesky(dd, true, 1, s);
     hipLaunchKernelGGL(k_cov_nlast, dim3((unsigned)(((size_t)Pp * CB + 255) / 256)), dim3(256), 0, s, dd);
     hipLaunchKernelGGL(k_cov_pivots, dim3(1), dim3(256), 0, s, dd, d0.p, fail.p);
-    hipLaunchKernelGGL(k_cov_syrk, dim3(T, T), dim3(256), 0, s, Ninv.p, Pp, Pp, Sig.p);
+    hipLaunchKernelGGL(k_cov_syrk, dim3(T, T), dim3(256), 0, s, work.Ninv.p, Pp, Pp, Sig.p);
     if (dump) PLBA_HIPCK(p, keep(Sig.p, p->cov_dbg_Sigma));
     // 5. landmarks, 6. keyframe / pair blocks
     double* o_pt = out.p + n_out - L - (size_t)Nl * 36 - (size_t)Np * 9;

@@ -23,12 +23,12 @@
 #include <vector>
 
 #include "plba.h"
+#include "plba_dense_work.h"
+#include "plba_mailbox.h"
 #include "plba_math.h"
 #include "plba_twin_plan.h"
 
 namespace plba {
-
-constexpr int TILE = 64;          // dense tile edge (wavefront-wide)
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of a kernel: raise it once per (device, kernel), under a
 // lock, and report a failure instead of letting the launch that needs the LDS fail later.
@@ -46,19 +46,6 @@ inline hipError_t ensure_dyn_lds(const void* func, int bytes) {
     return e;
 }
 constexpr int MAX_PART = 8192;    // per-block partial sums for deterministic reductions
-
-// LM control block, device-resident; copied back once per trial.
-struct Ctrl {
-    double lambda, ni, current_chi, temp_chi, scale, rho, maxdiag, pad0;
-    int accepted, solver_ok, iteration, trial, n_gate_pt, n_gate_ln, n_fail, sync_fail /* an in-launch wait ran into its bound */;
-};
-// Pinned, device-mapped host memory k_decide writes the control block into at the end of every LM trial: the host
-// polls `seq` instead of paying for a device-to-host copy launch plus a stream synchronisation per trial.
-struct Mailbox {
-    Ctrl c;
-    unsigned long long seq;
-    plba_trace_row row;      // the trial's trace row (also appended to the device-side trace): the host keeps the trace from here, no read-back at the end of a call
-};
 
 // one chunk (<= 256 entries) of a keyframe pair's entry list: everything k_schur_pairs needs to know up front, 32 bytes
 struct ChunkMeta { int32_t slot /* index in pair-major order: where its partial sums go */, start, end, ij /* i | j << 16 */, nch, ch0 /* the pair's chunks: slots [ch0, ch0 + nch) */, oi, oj /* kf_off_pvr of i, j */; };
@@ -239,7 +226,6 @@ int  edge_blocks(const DevBuf& d);
 
 // dense
 // chain-variable elimination ahead of the dense factorisation (plba_chain.hip)
-constexpr int NINV_MAX_T = 32;   // explicit-inverse back-substitution up to this many 32-wide block steps (longer sums would outlast the pivot sweep)
 constexpr int CHAIN_SEG = 8;      // at most this many chain blocks between two separators (one workgroup eliminates a segment)
 constexpr int CHAIN_NSLOT = 15;   // dense columns a keyframe position can own: 6 pose + 9 separator chain dimensions
 struct ChainView {

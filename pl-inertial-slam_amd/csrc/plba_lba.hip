@@ -36,13 +36,7 @@ struct LbaCtl {
     double err, err_prev, lambda, lambda_next, err_first, dx2;
     int iters, updates, do_update, done, failed, pad;
 };
-struct LbaMail {       // laid over the problem's mapped Mailbox (plba_internal.h): same size, `seq` at the same offset
-    LbaCtl c;
-    char pad[sizeof(Ctrl) - sizeof(LbaCtl)];
-    unsigned long long seq;
-    char pad2[sizeof(Mailbox) - sizeof(Ctrl) - sizeof(unsigned long long)];
-};
-static_assert(sizeof(LbaCtl) <= sizeof(Ctrl) && sizeof(LbaMail) == sizeof(Mailbox) && offsetof(LbaMail, seq) == offsetof(Mailbox, seq), "the LBA mailbox reuses the problem's mapped mailbox");
+using LbaMail = MailOver<LbaCtl>;      // laid over the problem's mapped Mailbox (plba_mailbox.h)
 struct LbaDev {
     int K, Nkf, Np, Nl, Ep, El, P, Ppad, ld;
     double fx, fy, cx, cy, homog_th;
@@ -750,14 +744,13 @@ int plba_lba_visual(plba_problem* p, const plba_lba_options* opt, int K, const d
 
     HIPCK(p, hipSetDevice(p->device));
     hipStream_t s = p->stream;
-    const int P = 6 * Nkf, Ppad = std::max(TILE, (P + TILE - 1) / TILE * TILE), ld = Ppad;
+    const int P = 6 * Nkf, Ppad = dense_ppad(P), ld = Ppad;
     const size_t sysn = (size_t)(Ppad + TILE) * ld, nl = (size_t)3 * Np + (size_t)6 * Nl;
     const int nblk = (L + LM_NT - 1) / LM_NT;
-    DArr<double> dT, dZ, dXp, dXl, dTiw, dRec, dHll, dgl, dDl, dHpp, dgp, dpart, dscal, dDXl, sys, Lfac, xx, Linv, LT32, rd32, Ninv, dTout;
+    DArr<double> dT, dZ, dXp, dXl, dTiw, dRec, dHll, dgl, dDl, dHpp, dgp, dpart, dscal, dDXl, sys, dTout;
     DArr<int32_t> dloc, dlockf, dlms, dokf, dkfs, dkfo, dpent, dchunk;
     DArr<double> dUrec;
-    DArr<int> flags, cflags;
-    DArr<Ctrl> ctrl;
+    DenseWork work; DArr<Ctrl> ctrl;
     std::vector<double> hT(T_kf_w16, T_kf_w16 + (size_t)16 * K), hXl(std::max<size_t>(nl, 1), 0.0);
     if (Np) memcpy(hXl.data(), xyz3, (size_t)3 * Np * 8);
     if (Nl) memcpy(hXl.data() + 3 * (size_t)Np, pq6, (size_t)6 * Nl * 8);
@@ -769,10 +762,7 @@ int plba_lba_visual(plba_problem* p, const plba_lba_options* opt, int K, const d
         HIPCK(p, dpent.upload(pair_ent)); HIPCK(p, dchunk.upload(chunk)); HIPCK(p, dUrec.alloc((size_t)8 * E));
         HIPCK(p, dXp.alloc(P)); HIPCK(p, dTiw.alloc((size_t)24 * K)); HIPCK(p, dRec.alloc((size_t)REC * E)); HIPCK(p, dHll.alloc((size_t)21 * L)); HIPCK(p, dgl.alloc((size_t)6 * L));
         HIPCK(p, dDl.alloc((size_t)21 * L)); HIPCK(p, dHpp.alloc((size_t)21 * Nkf)); HIPCK(p, dgp.alloc(P)); HIPCK(p, dpart.alloc((size_t)2 * nblk)); HIPCK(p, dscal.alloc(4)); HIPCK(p, dDXl.alloc(nl));
-        HIPCK(p, sys.alloc(sysn)); HIPCK(p, Lfac.alloc(sysn)); HIPCK(p, xx.alloc(ld)); HIPCK(p, ctrl.alloc(1)); HIPCK(p, dTout.alloc((size_t)16 * K));
-        HIPCK(p, Linv.alloc((size_t)(Ppad / TILE) * TILE * TILE)); HIPCK(p, flags.alloc(Ppad / TILE)); HIPCK(p, LT32.alloc((size_t)Ppad * 64)); HIPCK(p, rd32.alloc(Ppad));
-        HIPCK(p, cflags.alloc((size_t)(Ppad / 32 + 2) * (Ppad / 32)));
-        if (Ppad / 32 <= NINV_MAX_T) HIPCK(p, Ninv.alloc((size_t)2 * Ppad * ld));
+        HIPCK(p, sys.alloc(sysn)); HIPCK(p, ctrl.alloc(1)); HIPCK(p, dTout.alloc((size_t)16 * K)); HIPCK(p, work.alloc(Ppad, ld, ninv_fits(Ppad)));
         HIPCK(p, plba_stream_wait(p, s));
     }
     LbaDev d; memset(&d, 0, sizeof d);
@@ -781,11 +771,9 @@ int plba_lba_visual(plba_problem* p, const plba_lba_options* opt, int K, const d
     d.Tmap = dT.p; d.kf_loc = dloc.p; d.loc_kf = dlockf.p; d.lm_start = dlms.p; d.obs_kf = dokf.p; d.obs_z = dZ.p; d.kf_start = dkfs.p; d.kf_obs = dkfo.p;
     d.Xp = dXp.p; d.Xl = dXl.p; d.Tiw = dTiw.p; d.rec = dRec.p; d.Hll = dHll.p; d.gl = dgl.p; d.Dl = dDl.p; d.Hpp = dHpp.p; d.gp = dgp.p;
     d.urec = dUrec.p; d.pair_ent = dpent.p; d.chunk = dchunk.p; d.nchunk = nchunk;
-    d.part = dpart.p; d.scal = dscal.p; d.DXl = dDXl.p; d.sys = sys.p; d.x = xx.p; d.ctrl = ctrl.p; d.Tout = dTout.p;
+    d.part = dpart.p; d.scal = dscal.p; d.DXl = dDXl.p; d.sys = sys.p; d.x = work.x.p; d.ctrl = ctrl.p; d.Tout = dTout.p;
     DevBuf dd; memset(&dd, 0, sizeof dd);
-    dd.P = P; dd.Ppad = Ppad; dd.ld = ld; dd.sys = sys.p; dd.Lfac = Lfac.p; dd.x = xx.p; dd.ctrl = ctrl.p; dd.Linv = Linv.p; dd.flow_flags = flags.p; dd.LTblk = LT32.p; dd.Linv32 = LT32.p; dd.rdblk = rd32.p;
-    dd.fb = (p->opt.factor_block == 64) ? 64 : 32; dd.chol_flags = cflags.p; dd.flow = p->opt.factor_flow != 0; dd.wide = p->opt.wide_steps != 0 && !dd.flow;
-    if (Ninv.p) { dd.Ninv = Ninv.p; dd.Nwork = Ninv.p + (size_t)Ppad * ld; }
+    dd.P = P; dd.Ppad = Ppad; dd.ld = ld; dd.sys = sys.p; dd.ctrl = ctrl.p; work.bind(dd, p->opt);
 
     // ---- device-side control block + the problem's mapped mailbox ---------------------------------------------------------------------
     DArr<LbaCtl> dctl;
@@ -796,8 +784,7 @@ int plba_lba_visual(plba_problem* p, const plba_lba_options* opt, int K, const d
     d.ctl = dctl.p; d.mail = reinterpret_cast<LbaMail*>(p->d_mail);
     d.lambda_k = opt->lambda_k; d.min_error = opt->min_error; d.min_error_change = opt->min_error_change; d.variant = opt->variant;
     volatile LbaMail* hm = reinterpret_cast<volatile LbaMail*>(p->h_mail);
-    const unsigned long long seq0 = p->mail_seq;      // sequence numbers go on from the problem's: never one the mailbox has held before
-    p->mail_seq += (unsigned long long)std::max(opt->max_iters, 0) + 1;
+    const unsigned long long seq0 = mail_reserve(p, (unsigned long long)std::max(opt->max_iters, 0));
 
     const bool ltime = (p->opt.diag & PLBA_DIAG_TIMING) != 0;
     if (ltime) HIPCK(p, plba_stream_wait(p, s));
@@ -823,14 +810,7 @@ int plba_lba_visual(plba_problem* p, const plba_lba_options* opt, int K, const d
         hipLaunchKernelGGL(k_lba_update, grid(std::max<size_t>(nl, Nkf), 256), dim3(256), 0, s, d, nblk);
         hipLaunchKernelGGL(k_lba_post, dim3(1), dim3(1), 0, s, d, it, seq);
         // one pass behind: has pass it - 1 ended the run?  (pass `it` is in the queue already, the device never waits for this)
-        if (it > 0) {
-            const unsigned long long want = seq - 1;
-            long spins = 0;
-            while (__atomic_load_n(const_cast<const unsigned long long*>(&hm->seq), __ATOMIC_ACQUIRE) < want) {      // (what the mailbox held before is <= seq0)
-                if (++spins > (1L << 22)) { HIPCK(p, plba_stream_wait(p, s)); break; }
-            }
-            if (hm->c.done) stop = true;
-        }
+        if (it > 0) { HIPCK(p, mail_wait(p, s, seq - 1)); if (hm->c.done) stop = true; }      // (what the mailbox held before is <= seq0)
     }
     hipLaunchKernelGGL(k_lba_final, grid(K, 64), dim3(64), 0, s, d);
     HIPCK(p, plba_d2h(p, T_out16, dTout.p, (size_t)16 * K * 8));

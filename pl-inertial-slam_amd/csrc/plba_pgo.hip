@@ -54,14 +54,7 @@ struct PgoCtl {
     int done, iters, trials, stop_reason, n_trace, pad0, pad1;
 };
 struct PgoHead { int done, iters, trials, pad; };
-struct PgoMail {            // laid over the problem's mapped Mailbox (plba_internal.h): same size, `seq` at the same offset
-    PgoHead h;
-    char pad[sizeof(Ctrl) - sizeof(PgoHead)];
-    unsigned long long seq;
-    char pad2[sizeof(Mailbox) - sizeof(Ctrl) - sizeof(unsigned long long)];
-};
-static_assert(sizeof(PgoHead) <= sizeof(Ctrl) && sizeof(PgoMail) == sizeof(Mailbox) && offsetof(PgoMail, seq) == offsetof(Mailbox, seq),
-              "the pose-graph mailbox reuses the problem's mapped mailbox");
+using PgoMail = MailOver<PgoHead>;      // laid over the problem's mapped Mailbox (plba_mailbox.h)
 
 struct PgoDev {
     int nv, ne, n, P, Ppad, ld, nblk, max_iters, max_trials, trace_cap;
@@ -320,7 +313,7 @@ __global__ __launch_bounds__(64) void k_pgo_update(PgoDev d) {
 }
 
 __device__ void pgo_deliver(const PgoDev& d, unsigned long long seq) {
-    d.mail->h.done = d.ctl->done; d.mail->h.iters = d.ctl->iters; d.mail->h.trials = d.ctl->trials;
+    d.mail->c.done = d.ctl->done; d.mail->c.iters = d.ctl->iters; d.mail->c.trials = d.ctl->trials;
     __threadfence_system();
     __hip_atomic_store(&d.mail->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
@@ -514,7 +507,7 @@ int plba_optimize_pose_graph(plba_problem* p, plba_pose_graph* g, int max_iters,
     // ---- device ------------------------------------------------------------------------------------------------------------------
     HIPCK(p, hipSetDevice(p->device));
     hipStream_t s = p->stream;
-    const int Ppad = std::max(TILE, (P + TILE - 1) / TILE * TILE), ld = Ppad;
+    const int Ppad = dense_ppad(P), ld = Ppad;
     const size_t sysn = run && !sparse ? (size_t)(Ppad + TILE) * ld : 1;
     std::vector<double> Zi((size_t)12 * std::max(ne, 1), 0.0), info((size_t)36 * std::max(ne, 1), 0.0);
     for (int k = 0; k < ne; ++k) {
@@ -527,9 +520,9 @@ int plba_optimize_pose_graph(plba_problem* p, plba_pose_graph* g, int max_iters,
     if (free_v.empty()) free_v.assign(1, 0);
     auto nz = [](std::vector<int32_t>& v) { if (v.empty()) v.assign(1, 0); };
     nz(blk_start); nz(blk_src); nz(blk_diag); nz(blk_row); nz(dg_blk); nz(blkmap);
-    DArr<double> dX, dXs, dZi, dInfo, dErec, dEchi, dHblk, db, sys, Lfac, xx, Linv, LT32, rd32, Ninv;
+    DArr<double> dX, dXs, dZi, dInfo, dErec, dEchi, dHblk, db, sys, xx /* the sparse solve's */;
     DArr<int32_t> dfree, dei, dej, dbs, dbsrc, dbdiag, dbrow, ddg, dmap;
-    DArr<int> dcnt, flags, cflags;
+    DArr<int> dcnt; DenseWork work;
     DArr<int32_t> sp_m, sp_np, sp_row0, sp_rows, sp_umap, sp_chs, sp_ch, sp_ass, sp_as, sp_lv;
     DArr<long long> sp_off, sp_roff;
     DArr<double> sp_F, sp_R;
@@ -556,10 +549,7 @@ int plba_optimize_pose_graph(plba_problem* p, plba_pose_graph* g, int max_iters,
                 if (plan.ch.empty()) plan.ch.assign(1, 0);
                 HIPCK(p, sp_ch.upload(plan.ch)); HIPCK(p, sp_F.alloc((size_t)plan.fsize, false)); HIPCK(p, sp_R.alloc((size_t)plan.rsize, false));
             } else {
-                HIPCK(p, sys.alloc(sysn, false)); HIPCK(p, Lfac.alloc(sysn)); HIPCK(p, xx.alloc(ld));
-                HIPCK(p, Linv.alloc((size_t)(Ppad / TILE) * TILE * TILE)); HIPCK(p, flags.alloc(Ppad / TILE)); HIPCK(p, LT32.alloc((size_t)Ppad * 64)); HIPCK(p, rd32.alloc(Ppad));
-                HIPCK(p, cflags.alloc((size_t)(Ppad / 32 + 2) * (Ppad / 32)));
-                if (Ppad / 32 <= NINV_MAX_T) HIPCK(p, Ninv.alloc((size_t)2 * Ppad * ld));
+                HIPCK(p, sys.alloc(sysn, false)); HIPCK(p, work.alloc(Ppad, ld, ninv_fits(Ppad)));
             }
         }
         HIPCK(p, plba_stream_wait(p, s));
@@ -569,7 +559,7 @@ int plba_optimize_pose_graph(plba_problem* p, plba_pose_graph* g, int max_iters,
     d.tau = p->opt.tau; d.lower = p->opt.good_step_lower; d.upper = p->opt.good_step_upper; d.user_lambda = user_lambda_init;
     d.X = dX.p; d.Xs = dXs.p; d.cnt = dcnt.p; d.free_v = dfree.p; d.ei = dei.p; d.ej = dej.p; d.Zi = dZi.p; d.info = dInfo.p;
     d.erec = dErec.p; d.echi = dEchi.p; d.blk_start = dbs.p; d.blk_src = dbsrc.p; d.blk_diag = dbdiag.p; d.blk_row = dbrow.p; d.dg_blk = ddg.p; d.blkmap = dmap.p;
-    d.Hblk = dHblk.p; d.b = db.p; d.sys = sys.p; d.x = xx.p; d.ctl = dctl.p; d.mail = reinterpret_cast<PgoMail*>(p->d_mail); d.trace = dtrace.p;
+    d.Hblk = dHblk.p; d.b = db.p; d.sys = sys.p; d.x = sparse ? xx.p : work.x.p; d.ctl = dctl.p; d.mail = reinterpret_cast<PgoMail*>(p->d_mail); d.trace = dtrace.p;
     PgoSparseDev sd; memset(&sd, 0, sizeof sd);
     if (sparse && run) {
         sd.f_m = sp_m.p; sd.f_np = sp_np.p; sd.f_row0 = sp_row0.p; sd.rows = sp_rows.p; sd.umap = sp_umap.p; sd.ch_start = sp_chs.p; sd.ch = sp_ch.p;
@@ -583,9 +573,7 @@ int plba_optimize_pose_graph(plba_problem* p, plba_pose_graph* g, int max_iters,
         p->pgo_sparse[6] = (double)bytes;
     }
     DevBuf dd; memset(&dd, 0, sizeof dd);
-    dd.P = P; dd.Ppad = Ppad; dd.ld = ld; dd.sys = sys.p; dd.Lfac = Lfac.p; dd.x = xx.p; dd.ctrl = &dctl.p->c; dd.Linv = Linv.p; dd.flow_flags = flags.p; dd.LTblk = LT32.p; dd.Linv32 = LT32.p; dd.rdblk = rd32.p;
-    dd.fb = (p->opt.factor_block == 64) ? 64 : 32; dd.chol_flags = cflags.p; dd.flow = p->opt.factor_flow != 0; dd.wide = p->opt.wide_steps != 0 && !dd.flow;
-    if (Ninv.p) { dd.Ninv = Ninv.p; dd.Nwork = Ninv.p + (size_t)Ppad * ld; }
+    dd.P = P; dd.Ppad = Ppad; dd.ld = ld; dd.sys = sys.p; dd.ctrl = &dctl.p->c; work.bind(dd, p->opt);
 
     const dim3 eg((unsigned)((std::max(ne, 1) + 63) / 64)), vg((unsigned)((n + 63) / 64)), bg((unsigned)((std::max(nblk, 1) + 3) / 4)), fg((unsigned)((ld + 255) / 256), (unsigned)(Ppad + TILE));
     if (!run) {
@@ -594,8 +582,7 @@ int plba_optimize_pose_graph(plba_problem* p, plba_pose_graph* g, int max_iters,
     } else {
         const int max_steps = max_iters * std::max(p->opt.max_trials, 1);
         volatile PgoMail* hm = reinterpret_cast<volatile PgoMail*>(p->h_mail);
-        const unsigned long long seq0 = p->mail_seq;      // sequence numbers go on from the problem's: never one the mailbox has held before
-        p->mail_seq += (unsigned long long)max_steps + 1;
+        const unsigned long long seq0 = mail_reserve(p, (unsigned long long)max_steps);
         for (int step = 0; step < max_steps; ++step) {
             const unsigned long long seq = seq0 + (unsigned long long)step + 1;
             hipLaunchKernelGGL(k_pgo_edges<true>, eg, dim3(64), 0, s, d);
@@ -611,14 +598,8 @@ int plba_optimize_pose_graph(plba_problem* p, plba_pose_graph* g, int max_iters,
             hipLaunchKernelGGL(k_pgo_edges<false>, eg, dim3(64), 0, s, d);
             hipLaunchKernelGGL(k_pgo_decide, dim3(1), dim3(256), 0, s, d, seq);
             HIPCK(p, hipGetLastError());
-            if (step > 0) {      // one step behind: has step - 1 ended the run?  (this step is in the queue already)
-                const unsigned long long want = seq - 1;
-                long spins = 0;
-                while (__atomic_load_n(const_cast<const unsigned long long*>(&hm->seq), __ATOMIC_ACQUIRE) < want) {      // (what the mailbox held before is <= seq0)
-                    if (++spins > (1L << 22)) { HIPCK(p, plba_stream_wait(p, s)); break; }
-                }
-                if (hm->h.done) break;
-            }
+            // one step behind: has step - 1 ended the run?  (this step is in the queue already; what the mailbox held before is <= seq0)
+            if (step > 0) { HIPCK(p, mail_wait(p, s, seq - 1)); if (hm->c.done) break; }
         }
     }
     HIPCK(p, plba_stream_wait(p, s));

@@ -129,7 +129,7 @@ struct DArr {
     const DevBatch* bsrc = nullptr;      // ... of this batch (the per-window one or the pose structure's)
     void drop_batched() { if (batched) { p = nullptr; n = 0; cls = 0; batched = false; } }
     // null unless the buffer is a pool block or a batched one of the CURRENT generation: for the conditionally allocated buffers
-    // (d_imu_loc, d_ob_err, d_Ninvd, d_pr_H, d_lmg_*), whose previous window's pointer would alias another buffer's memory
+    // (d_imu_loc, d_ob_err, dwork.Ninv, d_pr_H, d_lmg_*), whose previous window's pointer would alias another buffer's memory
     T* checked() const { return (batched && bsrc && bgen != bsrc->gen) ? nullptr : p; }
     void expire() { if (batched && bsrc && bgen != bsrc->gen) drop_batched(); }
     hipError_t alloc(size_t cnt, bool zero = true) {
@@ -198,9 +198,28 @@ struct DArr {
     ~DArr() { release(); }
 };
 
-}  // namespace plba
+// What launch_cholesky / launch_trsv_back work in besides the system itself, and the DevBuf fields that name it: every caller of the two
+// launchers holds one.  Sizes: plba_dense_work.h.  `sys`, `ctrl`, P, Ppad and ld stay with the caller, who comes by `sys` in its own way.
+struct DenseWork {
+    DArr<double> Lfac, x, Linv, LT32, rd32, Ninv;
+    DArr<int> flow_flags, chol_flags;
+    size_t nwork = 0;      // where Nwork starts in Ninv; 0: this allocation keeps no explicit inverse (Ninv.p may be an earlier one's block)
+    // under the caller's DArrStreamScope and DevBatch; whether the inverse is kept is the caller's decision (want_ninv, or alloc_ninv() later): they share ninv_fits()
+    hipError_t alloc(int Ppad, int ld, bool want_ninv, bool zero = true) {
+        const DenseCounts n = dense_counts(Ppad, ld); hipError_t e; nwork = 0;
+        if ((e = Lfac.alloc(n.sys_len, zero)) || (e = x.alloc(n.x, zero)) || (e = Linv.alloc(n.Linv, zero)) || (e = LT32.alloc(n.LT32, zero)) ||
+            (e = rd32.alloc(n.rd32, zero)) || (e = flow_flags.alloc(n.flow_flags, zero)) || (e = chol_flags.alloc(n.chol_flags, zero))) return e;
+        return want_ninv ? alloc_ninv(Ppad, ld, zero) : hipSuccess;
+    }
+    hipError_t alloc_ninv(int Ppad, int ld, bool zero = true) { nwork = (size_t)Ppad * ld; return Ninv.alloc(dense_counts(Ppad, ld).ninv, zero); }
+    void bind_ninv(DevBuf& dd) const { dd.Ninv = nwork ? Ninv.p : nullptr; dd.Nwork = dd.Ninv ? dd.Ninv + nwork : nullptr; }
+    void bind(DevBuf& dd, const plba_options& o) const {
+        dd.Lfac = Lfac.p; dd.x = x.p; dd.Linv = Linv.p; dd.LTblk = LT32.p; dd.Linv32 = LT32.p /* shares LTblk's storage */; dd.rdblk = rd32.p;
+        dd.flow_flags = flow_flags.p; dd.chol_flags = chol_flags.p; dd.fb = o.factor_block == 64 ? 64 : 32; dd.flow = o.factor_flow != 0; dd.wide = o.wide_steps != 0 && !dd.flow; bind_ninv(dd);
+    }
+    void expire() { Lfac.expire(); x.expire(); Linv.expire(); LT32.expire(); rd32.expire(); Ninv.expire(); flow_flags.expire(); chol_flags.expire(); }
+};
 
-namespace plba {
 struct MargPending;      // a plba_marginalize_to_prior still in the stream (plba_marg.hip)
 struct BowState;         // the vocabularies and the keyframe database of place recognition (plba_bow.hip)
 // host image of the fused landmark-major passes' group structure (build_lm_groups, plba_api.hip); kept with the cached context
@@ -343,8 +362,8 @@ struct plba_problem {
     plba::DArr<int32_t> d_pr_kf, d_pr_isbias, d_pr_size, d_pr_idx, d_pr_x0off, d_pr_off;
     plba::DArr<double> d_pr_x0, d_pr_J0, d_pr_r0, d_pr_err, d_pr_dx, d_pr_chi, d_pr_H;
     plba::DArr<double> d_bprior, d_bprior2;
-    plba::DArr<double> d_Hconst, d_Himu, d_bimu, d_Himu2, d_bimu2, d_sys, d_Lfac, d_bpg, d_x, d_Linv, d_LT32, d_rd32;
-    plba::DArr<int> d_flow_flags, d_chol_flags;
+    plba::DArr<double> d_Hconst, d_Himu, d_bimu, d_Himu2, d_bimu2, d_sys, d_bpg;
+    plba::DenseWork work;                       // the pose-side system's solver workspace (its Ninv comes with the structure: StructCache)
     int flow_epoch = 0;
     plba::DArr<double> d_chi_part, d_scale_part, d_maxd_part, d_kfdiag, d_red, d_posediag, d_xbuf;
     plba::DArr<plba::Ctrl> d_ctrl;
@@ -359,8 +378,8 @@ struct plba_problem {
     plba::ChainView cv{};
     plba::DevBuf dd{};
     plba::DArr<int32_t> d_cidx, d_pidx, d_epos, d_seg_start, d_seg_col, d_ppos, d_pslot, d_slotcol;
-    plba::DArr<double> d_W, d_Ldinv, d_Lsub, d_sysd, d_Lfacd, d_xd, d_Linvd, d_LT32d, d_rd32d, d_Ninv, d_Ninvd, d_dbgbuf;
-    plba::DArr<int> d_flow_flagsd, d_chol_flagsd;
+    plba::DArr<double> d_W, d_Ldinv, d_Lsub, d_sysd, d_dbgbuf;
+    plba::DenseWork dwork;                      // ... and the compact system's (`dd`)
     bool band_ok = false;                       // the compact dense system is banded: twisted in-LDS solver (plba_band.hip)
     plba::BandView bandv{};
     plba::DArr<double> d_band_L, d_band_y, d_band_mid;
@@ -412,6 +431,18 @@ inline hipError_t plba_stream_wait(hipStream_t s, double spin_ms = 50.0) {
 }
 // ... on behalf of a problem: counted (plba_problem::host_waits)
 inline hipError_t plba_stream_wait(plba_problem* p, hipStream_t s) { ++p->host_waits; return plba_stream_wait(s); }
+
+// The host side of the mapped mailbox (plba_mailbox.h).  A problem's sequence numbers only grow, so the mailbox never holds one a later
+// call is going to wait for.  mail_reserve: a loop of up to n deliveries uses seq0 + 1 .. seq0 + n.
+inline unsigned long long mail_reserve(plba_problem* p, unsigned long long n) { p->mail_seq += n + 1; return p->mail_seq - n - 1; }
+// Spin until the device has delivered `want` (or a later number); after 2^22 loads (~ tens of ms) a real synchronisation instead, which
+// also surfaces a device error.  plba_optimize waits for the newest number issued, which the mailbox cannot be past: there `seq < want`
+// is `seq != want`, and the caller's own check of equality afterwards stays.
+inline hipError_t mail_wait(plba_problem* p, hipStream_t s, unsigned long long want) {
+    for (long spins = 0; __atomic_load_n(&p->h_mail->seq, __ATOMIC_ACQUIRE) < want;)
+        if (++spins > (1L << 22)) return plba_stream_wait(p, s);
+    return hipSuccess;
+}
 
 // Copies between device memory and CALLER-OWNED (pageable) host memory go through the context's pinned staging area.
 // Handing a pageable pointer to hipMemcpy makes the runtime pin (register) those pages with the GPU for transfers above its
