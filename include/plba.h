@@ -41,7 +41,8 @@ typedef enum {
     PLBA_ERR_STATE = -2,     /* call order violated (e.g. optimize before upload)    */
     PLBA_ERR_DEVICE = -3,    /* HIP runtime error, no device, kernel image missing    */
     PLBA_ERR_NUMERIC = -4,   /* non-finite input                                       */
-    PLBA_ERR_EXCHANGE = -5   /* the multi-GPU exchange callback failed                 */
+    PLBA_ERR_EXCHANGE = -5,  /* the multi-GPU exchange callback failed                 */
+    PLBA_ERR_INTERNAL = -6   /* a plan failed the library's own checks before a launch */
 } plba_status;
 
 /* Edge families of the path. */
@@ -460,6 +461,8 @@ typedef struct plba_lba_options {
                                    with `int Hmax` (:2468: lambda scales with the truncated maximum), the error divided by the zero
                                    counters in EVERY pass (:2744: every step is taken) — and machine epsilon for both thresholds
                                    (:2746, :2776), which the caller passes as min_error / min_error_change */
+    int    solver;              /* linear solver of the 6 Nkf reduced camera system: 0 = dense Cholesky (the default), 1 = sparse
+                                   multifrontal Cholesky on the covisibility graph (see plba_lba_visual); anything else is refused */
 } plba_lba_options;
 typedef struct plba_lba_stats {
     int    iterations;          /* linear solves performed */
@@ -476,7 +479,22 @@ void plba_lba_default_options(plba_lba_options* o);
  * x_kf_w is taken as logmap_se3 of it).  xyz3 (Np x 3) / pq6 (Nl x 6): in = map estimates, out = optimised.
  * Observations are landmark-major as localBundleAdjustment builds its lists.  T_out16: K x 16, the optimised poses
  * (unchanged for kf_loc = -1).  pt_moved / ln_moved (optional): 1 where the landmark moved more than 1 cm, for which the
- * reference clears `inlier` (:1944-1970).  `p` supplies the device, the stream and the error text. */
+ * reference clears `inlier` (:1944-1970).  `p` supplies the device, the stream and the error text.
+ * Linear solver (options->solver): 0 = the landmark blocks are eliminated and the 6 Nkf reduced camera system is factored as a dense
+ * matrix, O(Nkf^2) memory and O(Nkf^3) time per pass.  1 = the same reduced system kept as a list of 6 x 6 blocks, one per local
+ * keyframe and one per pair of local keyframes that observe a common landmark, and solved by the multifrontal Cholesky of
+ * plba_optimize_pose_graph's sparse path (nested dissection and symbolic factorisation once per call on the host, then per pass:
+ * the blocks summed in a fixed order without floating-point atomics, assembled into the fronts, factored up the elimination tree and
+ * back-substituted down it); memory grows with the fill of L and nothing of size Nkf x Nkf exists on the host or the device: the
+ * solver for whole-map runs (globalBundleAdjustment: variant = 1, solver = 1).  Both solvers run the same LM text with the same
+ * exits and the same solver_failed meaning (a pivot <= 0 or not finite, in a landmark block or in the pose system, ends the run
+ * with no update), for both variants and for use_iterate_poses 0 and 1; their results agree to rounding (another elimination order),
+ * and the sparse path is bit-reproducible from call to call.  A plan that fails its own index checks makes the call fail with
+ * PLBA_ERR_INTERNAL before anything is launched; there is no fall-back to the dense solver.  options->solver other than 0 or 1:
+ * PLBA_ERR_INVALID, outputs untouched.  plba_debug_get(p, "lba_sparse") (8, at any time) describes the last plba_lba_visual: [0] 1
+ * if it took the sparse path, [1] local keyframes, [2] fronts, [3] tree levels, [4] nonzero 6 x 6 blocks of L, [5] largest front
+ * dimension, [6] device bytes the call allocated for the pose system (block list, fronts, right-hand side and solution), [7] host
+ * ms of the analysis; all 0 before the first call, after a dense call and after a refused one. */
 int plba_lba_visual(plba_problem* p, const plba_lba_options* opt, int K, const double* T_kf_w16, const int32_t* kf_loc,
                     int Np, double* xyz3, int Nl, double* pq6,
                     int Ep, const int32_t* po_pt, const int32_t* po_kf, const double* uv2,
@@ -831,6 +849,7 @@ int  plba_bow_reset(plba_problem* p);
  * system S = Hpp - sum Hpl Hr^-1 Hlp as the device built it, and Sigma_pp = S^-1 as the device formed it, in the pose-side index order;
  * "host_waits" (1, at any time, waits for nothing): how often the library has blocked the calling thread on the device;
  * "pgo_sparse" (8, at any time): the last plba_optimize_pose_graph's solver (see there);
+ * "lba_sparse" (8, at any time): the last plba_lba_visual's solver (see there);
  * "bow_db" (5, at any time): the place-recognition database, [keyframes, live keyframes, stored entries of the point vectors, of the
  * line vectors, device bytes held]. */
 int plba_debug_build(plba_problem* p, double lambda, int do_solve);

@@ -16,7 +16,7 @@ c_uint8_p = C.POINTER(C.c_uint8)
 EDGE_POINT, EDGE_LINE, EDGE_IMU_PVR, EDGE_IMU_BIAS, EDGE_PRIOR = range(5)
 
 STATUS = {0: "PLBA_OK", -1: "PLBA_ERR_INVALID", -2: "PLBA_ERR_STATE", -3: "PLBA_ERR_DEVICE",
-          -4: "PLBA_ERR_NUMERIC", -5: "PLBA_ERR_EXCHANGE"}
+          -4: "PLBA_ERR_NUMERIC", -5: "PLBA_ERR_EXCHANGE", -6: "PLBA_ERR_INTERNAL"}
 
 
 class Options(C.Structure):
@@ -49,7 +49,8 @@ class Prior(C.Structure):
 
 class LbaOptions(C.Structure):
     _fields_ = [("lambda_lm", C.c_double), ("lambda_k", C.c_double), ("max_iters", C.c_int), ("homog_th", C.c_double),
-                ("min_error", C.c_double), ("min_error_change", C.c_double), ("use_iterate_poses", C.c_int), ("variant", C.c_int)]
+                ("min_error", C.c_double), ("min_error_change", C.c_double), ("use_iterate_poses", C.c_int), ("variant", C.c_int),
+                ("solver", C.c_int)]
 
 
 class LbaStats(C.Structure):

@@ -54,6 +54,7 @@ static void reset_for_reuse(plba_problem* p, const plba_options* opt) {
     p->pr_n = p->pr_nv = 0; p->pr_vid.clear(); p->pr_size.clear(); p->pr_idx.clear(); p->pr_x0.clear(); p->pr_J0.clear(); p->pr_r0.clear();
     p->prior_dev = false; p->prior_changed = false; p->pr_m = 0; p->host_waits = 0;
     for (double& v : p->pgo_sparse) v = 0.0;
+    for (double& v : p->lba_sparse) v = 0.0;
     memset(&p->rob, 0, sizeof p->rob);
     p->rank = 0; p->world = 1; p->xfn = nullptr; p->xuser = nullptr;
     p->dirty = true; p->P = p->Ppad = p->ld = p->L = p->E = 0; p->cur = 0;
@@ -2668,7 +2669,12 @@ int plba_debug_get(plba_problem* p, const char* what, double* out, size_t cap, s
         for (size_t i = 0; out && i < cap && i < 8; ++i) out[i] = p->pgo_sparse[i];
         return PLBA_OK;
     }
-    if (w == "bow_db") {          // (host-side record of the place-recognition database)
+    if (w == "lba_sparse") {      // (host-side record of the last plba_lba_visual)
+        if (n) *n = 8;
+        for (size_t i = 0; out && i < cap && i < 8; ++i) out[i] = p->lba_sparse[i];
+        return PLBA_OK;
+    }
+    if (w == "bow_db") {       // (host-side record of the place-recognition database)
         double d5[5];
         plba_bow_describe(p, d5);
         if (n) *n = 5;

@@ -15,7 +15,14 @@
 // the reference's lists are) -> k_lba_posesys (workgroup per local keyframe over its observations) -> k_lba_reduce
 // -> [host: err, lambda] -> k_lba_sysinit -> k_lba_dinv -> k_lba_pairs -> k_lba_rhs -> Cholesky / back-substitution (plba_dense.hip)
 // -> k_lba_backsub -> k_lba_update (|DX|^2; the update itself gated on solver_ok) -> [host: |DX|].
+//
+// plba_lba_options.solver = 1 (the whole-map runs) keeps the reduced camera system as the list of its nonzero 6 x 6 blocks
+// (plba_lba_sparse.h) and replaces  memset + k_lba_sysinit + k_lba_pairs + Cholesky / back-substitution  by  k_lba_sblk (a wave per
+// block: its pair entries summed in a fixed order, no atomics) -> k_lba_rhs into a P-vector -> the multifrontal solve of
+// plba_pgo_sparse.h -> k_lba_smerge; everything else of a pass, and the control, is the same code.
 #include "plba_internal.h"
+#include "plba_lba_sparse.h"
+#include "plba_pgo_sparse.h"
 #include "plba_problem.h"
 #include <chrono>
 #include <cstddef>
@@ -68,8 +75,14 @@ struct LbaDev {
     double* part;              // 2 x nblk per-block partials: error sums (later the landmark part of |DX|^2), max |Hll_ii|
     double* scal;
     double* DXl;               // 3 Np + 6 Nl
-    double* sys;               // (Ppad + 64) x ld
-    double* x;                 // dense solution
+    double* sys;               // (Ppad + 64) x ld (dense solver only)
+    double* rhs;               // P: the right-hand side of the reduced system (dense: row Ppad of sys)
+    double* x;                 // P: its solution
+    const int32_t* sb_start;   // sparse solver: nsblk + 1, the pair entries of each block of the block list
+    const int32_t* sb_row;     // nsblk: lb
+    const int32_t* sb_col;     // nsblk: la <= lb
+    double* Hblk;              // nsblk x 36: block (lb, la) of the damped reduced system, row-major
+    Ctrl* lmctrl;              // sparse solver: k_lba_dinv's solver_ok (k_sps_assemble sets ctrl's afresh behind it)
     Ctrl* ctrl;
     double* Tout;              // K x 16
 };
@@ -561,7 +574,57 @@ __global__ void __launch_bounds__(KF_NT) k_lba_rhs(LbaDev d) {
         for (int a = 0; a < 6; ++a) acc[a] += r[a] * sg;
     }
     block_sum<6>(acc, sh);
-    if (threadIdx.x < 6) d.sys[(size_t)d.Ppad * d.ld + 6 * i + threadIdx.x] = d.gp[6 * i + threadIdx.x] - acc[0];
+    if (threadIdx.x < 6) d.rhs[6 * i + threadIdx.x] = d.gp[6 * i + threadIdx.x] - acc[0];
+}
+// The sparse solver's system: one wave per block (lb, la) of the block list.  An entry contributes what k_lba_pairs adds to S[la, lb],
+// here transposed into S[lb, la], the lower block the multifrontal solve assembles; lane t takes the entries t, t + 64, ... in their
+// list order, the 64 partial sums meet in a butterfly (both partners of a stage add the same two numbers, so every lane ends with the
+// same bits), and lanes 0 .. 35 store one value each: the block's sum subtracted from the damped Hpp on the diagonal, from zero
+// elsewhere.  Every sum has one fixed order and one writer: no atomics.
+__global__ void __launch_bounds__(64) k_lba_sblk(LbaDev d) {
+    if (d.ctl->done) return;
+    const int k = blockIdx.x, lane = threadIdx.x;
+    const int la = d.sb_col[k], lb = d.sb_row[k];
+    double acc[36];
+#pragma unroll
+    for (int q = 0; q < 36; ++q) acc[q] = 0.0;
+    for (int t = d.sb_start[k] + lane; t < d.sb_start[k + 1]; t += 64) {
+        const int ea = d.pair_ent[2 * (size_t)t], eb = d.pair_ent[2 * (size_t)t + 1];
+        const double* ra = d.rec + (size_t)REC * ea;
+        const double* rb = d.rec + (size_t)REC * eb;
+        const double* ua = d.urec + (size_t)8 * ea;
+        double c = 0.0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) c += ua[i] * rb[6 + i];
+        c *= rb[12];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            const double cj = c * ra[j];      // (the products of k_lba_pairs, stored at the transposed place)
+#pragma unroll
+            for (int i = 0; i < 6; ++i) acc[i * 6 + j] += cj * rb[i];
+        }
+    }
+    double mine = 0.0;
+#pragma unroll
+    for (int q = 0; q < 36; ++q) {
+        double v = acc[q];
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        if (lane == q) mine = v;
+    }
+    if (lane < 36) {
+        double h = 0.0;
+        if (la == lb) {
+            const int a = lane / 6, b = lane % 6, lo = a < b ? a : b, hi = a < b ? b : a;
+            h = d.Hpp[21 * la + diag_q(lo) + (hi - lo)];
+            if (a == b) h += d.ctl->lambda * h;      // the multiplicative damping, as k_lba_sysinit applies it
+        }
+        d.Hblk[(size_t)36 * k + lane] = h - mine;
+    }
+}
+// the landmark blocks' verdict (k_lba_dinv) joins the pose system's, which k_sps_assemble set afresh behind k_lba_dinv
+__global__ void k_lba_smerge(LbaDev d) {
+    if (d.ctl->done) return;
+    if (!d.lmctrl->solver_ok) d.ctrl->solver_ok = 0;
 }
 // dx_l = D (gl - sum_a w_a Jl_a (Jp_a . dx_pose(a)))
 template <int N>
@@ -667,6 +730,7 @@ void plba_lba_default_options(plba_lba_options* o) {
     o->min_error_change = 1e-7;      // Config::minErrorChange
     o->use_iterate_poses = 0;
     o->variant = 0;
+    o->solver = 0;            // the dense reduced-camera solve
 }
 
 int plba_lba_visual(plba_problem* p, const plba_lba_options* opt, int K, const double* T_kf_w16, const int32_t* kf_loc,
@@ -675,7 +739,10 @@ int plba_lba_visual(plba_problem* p, const plba_lba_options* opt, int K, const d
                     int El, const int32_t* lo_ln, const int32_t* lo_kf, const double* l3,
                     double fx, double fy, double cx, double cy, double* T_out16, uint8_t* pt_moved, uint8_t* ln_moved, plba_lba_stats* st) {
     if (!p) return PLBA_ERR_INVALID;
+    for (double& v : p->lba_sparse) v = 0.0;      // (a refused call leaves an all-zero record)
     if (!opt || K <= 0 || !T_kf_w16 || !kf_loc || Np < 0 || Nl < 0 || Ep < 0 || El < 0 || !T_out16 || !st) FAIL(p, PLBA_ERR_INVALID, "plba_lba_visual: null or negative argument");
+    if (opt->solver != 0 && opt->solver != 1) FAIL(p, PLBA_ERR_INVALID, "plba_lba_visual: options.solver = %d", opt->solver);
+    const bool sparse = opt->solver == 1;
     if (Ep + El == 0) FAIL(p, PLBA_ERR_INVALID, "plba_lba_visual: no observation");
     if ((Np && !xyz3) || (Nl && !pq6) || (Ep && (!po_pt || !po_kf || !uv2)) || (El && (!lo_ln || !lo_kf || !l3))) FAIL(p, PLBA_ERR_INVALID, "plba_lba_visual: missing array");
     // local keyframes: indices 0 .. Nkf-1, each once
@@ -712,7 +779,19 @@ int plba_lba_visual(plba_problem* p, const plba_lba_options* opt, int K, const d
     // Schur pair entries: for every landmark, every pair of its observations in local keyframes la <= lb (an observation with
     // itself included), grouped by keyframe pair and cut into chunks of <= PAIR_CHUNK entries; constant over the iterations
     std::vector<int32_t> pair_ent, chunk;
-    {
+    LbaBlockList blist;          // the sparse solver's: the same entries grouped by block of S, nothing of size Nkf x Nkf
+    PgoSparsePlan plan;
+    double srec[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // plba_debug_get "lba_sparse", kept when the call has succeeded
+    if (sparse) {
+        if (!lba_block_list(Nkf, L, lm_start.data(), obs_kf.data(), kf_loc, blist)) FAIL(p, PLBA_ERR_INVALID, "plba_lba_visual: too many co-observation pairs");
+        const auto ta = std::chrono::steady_clock::now();
+        if (!pgo_sparse_analyse(Nkf, blist.blk_row, blist.blk_col, plan)) FAIL(p, PLBA_ERR_INTERNAL, "plba_lba_visual: the sparse analysis failed its checks");
+        srec[7] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ta).count();
+        srec[0] = 1.0; srec[1] = Nkf; srec[2] = plan.nfront; srec[3] = plan.nlev; srec[4] = (double)plan.nnz_blk; srec[5] = plan.max_m;
+        pair_ent.swap(blist.pair_ent);
+        if (pair_ent.empty()) pair_ent.assign(2, 0);
+        if (plan.ch.empty()) plan.ch.assign(1, 0);
+    } else {
         std::vector<int64_t> cnt((size_t)Nkf * Nkf + 1, 0);
         auto for_pairs = [&](auto&& fn) {
             for (int l = 0; l < L; ++l)
@@ -750,7 +829,13 @@ int plba_lba_visual(plba_problem* p, const plba_lba_options* opt, int K, const d
     DArr<double> dT, dZ, dXp, dXl, dTiw, dRec, dHll, dgl, dDl, dHpp, dgp, dpart, dscal, dDXl, sys, dTout;
     DArr<int32_t> dloc, dlockf, dlms, dokf, dkfs, dkfo, dpent, dchunk;
     DArr<double> dUrec;
-    DenseWork work; DArr<Ctrl> ctrl;
+    DenseWork work; DArr<Ctrl> ctrl, lmctrl;
+    DArr<int32_t> sb_start, sb_row, sb_col, sp_m, sp_np, sp_row0, sp_rows, sp_umap, sp_chs, sp_ch, sp_ass, sp_as, sp_lv;      // the sparse solver's
+    DArr<long long> sp_off, sp_roff;
+    DArr<double> sp_F, sp_R, dHblk, db, xx;
+    Ctrl lm0; memset(&lm0, 0, sizeof lm0); lm0.solver_ok = 1;
+    const std::vector<Ctrl> hlm0(1, lm0);
+    const int nsblk = (int)blist.blk_row.size();
     std::vector<double> hT(T_kf_w16, T_kf_w16 + (size_t)16 * K), hXl(std::max<size_t>(nl, 1), 0.0);
     if (Np) memcpy(hXl.data(), xyz3, (size_t)3 * Np * 8);
     if (Nl) memcpy(hXl.data() + 3 * (size_t)Np, pq6, (size_t)6 * Nl * 8);
@@ -759,10 +844,20 @@ int plba_lba_visual(plba_problem* p, const plba_lba_options* opt, int K, const d
         DArrStreamScope staged(s, p->have_ctx ? p->ctx.stage : nullptr);      // host vectors above stay alive until the wait below
         HIPCK(p, dT.upload(hT)); HIPCK(p, dZ.upload(obs_z)); HIPCK(p, dXl.upload(hXl)); HIPCK(p, dloc.upload(hloc)); HIPCK(p, dlockf.upload(loc_kf));
         HIPCK(p, dlms.upload(lm_start)); HIPCK(p, dokf.upload(obs_kf)); HIPCK(p, dkfs.upload(kf_start)); HIPCK(p, dkfo.upload(kf_obs));
-        HIPCK(p, dpent.upload(pair_ent)); HIPCK(p, dchunk.upload(chunk)); HIPCK(p, dUrec.alloc((size_t)8 * E));
+        HIPCK(p, dpent.upload(pair_ent)); HIPCK(p, dUrec.alloc((size_t)8 * E));
         HIPCK(p, dXp.alloc(P)); HIPCK(p, dTiw.alloc((size_t)24 * K)); HIPCK(p, dRec.alloc((size_t)REC * E)); HIPCK(p, dHll.alloc((size_t)21 * L)); HIPCK(p, dgl.alloc((size_t)6 * L));
         HIPCK(p, dDl.alloc((size_t)21 * L)); HIPCK(p, dHpp.alloc((size_t)21 * Nkf)); HIPCK(p, dgp.alloc(P)); HIPCK(p, dpart.alloc((size_t)2 * nblk)); HIPCK(p, dscal.alloc(4)); HIPCK(p, dDXl.alloc(nl));
-        HIPCK(p, sys.alloc(sysn)); HIPCK(p, ctrl.alloc(1)); HIPCK(p, dTout.alloc((size_t)16 * K)); HIPCK(p, work.alloc(Ppad, ld, ninv_fits(Ppad)));
+        HIPCK(p, ctrl.alloc(1)); HIPCK(p, dTout.alloc((size_t)16 * K));
+        if (sparse) {      // the block list, the plan, the fronts; no sys, no DenseWork, no dense x
+            HIPCK(p, sb_start.upload(blist.blk_start)); HIPCK(p, sb_row.upload(blist.blk_row)); HIPCK(p, sb_col.upload(blist.blk_col));
+            HIPCK(p, dHblk.alloc((size_t)36 * nsblk)); HIPCK(p, db.alloc(P)); HIPCK(p, xx.alloc(P)); HIPCK(p, lmctrl.upload(hlm0));
+            HIPCK(p, sp_m.upload(plan.f_m)); HIPCK(p, sp_np.upload(plan.f_np)); HIPCK(p, sp_row0.upload(plan.f_row0)); HIPCK(p, sp_rows.upload(plan.rows));
+            HIPCK(p, sp_umap.upload(plan.umap)); HIPCK(p, sp_chs.upload(plan.ch_start)); HIPCK(p, sp_ch.upload(plan.ch)); HIPCK(p, sp_ass.upload(plan.as_start));
+            HIPCK(p, sp_as.upload(plan.as)); HIPCK(p, sp_lv.upload(plan.lv)); HIPCK(p, sp_off.upload(plan.f_off)); HIPCK(p, sp_roff.upload(plan.f_roff));
+            HIPCK(p, sp_F.alloc((size_t)plan.fsize, false)); HIPCK(p, sp_R.alloc((size_t)plan.rsize, false));
+        } else {
+            HIPCK(p, dchunk.upload(chunk)); HIPCK(p, sys.alloc(sysn)); HIPCK(p, work.alloc(Ppad, ld, ninv_fits(Ppad)));
+        }
         HIPCK(p, plba_stream_wait(p, s));
     }
     LbaDev d; memset(&d, 0, sizeof d);
@@ -773,7 +868,21 @@ int plba_lba_visual(plba_problem* p, const plba_lba_options* opt, int K, const d
     d.urec = dUrec.p; d.pair_ent = dpent.p; d.chunk = dchunk.p; d.nchunk = nchunk;
     d.part = dpart.p; d.scal = dscal.p; d.DXl = dDXl.p; d.sys = sys.p; d.x = work.x.p; d.ctrl = ctrl.p; d.Tout = dTout.p;
     DevBuf dd; memset(&dd, 0, sizeof dd);
-    dd.P = P; dd.Ppad = Ppad; dd.ld = ld; dd.sys = sys.p; dd.ctrl = ctrl.p; work.bind(dd, p->opt);
+    PgoSparseDev sd; memset(&sd, 0, sizeof sd);
+    if (sparse) {
+        d.x = xx.p; d.rhs = db.p; d.sb_start = sb_start.p; d.sb_row = sb_row.p; d.sb_col = sb_col.p; d.Hblk = dHblk.p; d.lmctrl = lmctrl.p;
+        sd.f_m = sp_m.p; sd.f_np = sp_np.p; sd.f_row0 = sp_row0.p; sd.rows = sp_rows.p; sd.umap = sp_umap.p; sd.ch_start = sp_chs.p; sd.ch = sp_ch.p;
+        sd.as_start = sp_ass.p; sd.as = sp_as.p; sd.lv = sp_lv.p; sd.f_off = sp_off.p; sd.f_roff = sp_roff.p; sd.F = sp_F.p; sd.R = sp_R.p;
+        sd.Hblk = dHblk.p; sd.b = db.p; sd.x = xx.p; sd.c = ctrl.p /* lambda = 0: the blocks are damped already */;
+        size_t bytes = 0;
+        auto add = [&](const auto& a) { bytes += a.n * sizeof(*a.p); };
+        add(dpent); add(sb_start); add(sb_row); add(sb_col); add(dHblk); add(db); add(xx); add(lmctrl); add(sp_m); add(sp_np); add(sp_row0); add(sp_rows);
+        add(sp_umap); add(sp_chs); add(sp_ch); add(sp_ass); add(sp_as); add(sp_lv); add(sp_off); add(sp_roff); add(sp_F); add(sp_R);
+        srec[6] = (double)bytes;
+    } else {
+        d.rhs = sys.p + (size_t)Ppad * ld;
+        dd.P = P; dd.Ppad = Ppad; dd.ld = ld; dd.sys = sys.p; dd.ctrl = ctrl.p; work.bind(dd, p->opt);
+    }
 
     // ---- device-side control block + the problem's mapped mailbox ---------------------------------------------------------------------
     DArr<LbaCtl> dctl;
@@ -782,6 +891,9 @@ int plba_lba_visual(plba_problem* p, const plba_lba_options* opt, int K, const d
     c0.err_prev = 999999999.9; c0.lambda = opt->lambda_lm; c0.lambda_next = opt->lambda_lm;
     HIPCK(p, plba_h2d(p, dctl.p, &c0, sizeof c0));
     d.ctl = dctl.p; d.mail = reinterpret_cast<LbaMail*>(p->d_mail);
+    sd.done = &dctl.p->done;
+    LbaDev dlm = d;      // k_lba_dinv's view: in the sparse solver its verdict goes to lmctrl
+    if (sparse) dlm.ctrl = lmctrl.p;
     d.lambda_k = opt->lambda_k; d.min_error = opt->min_error; d.min_error_change = opt->min_error_change; d.variant = opt->variant;
     volatile LbaMail* hm = reinterpret_cast<volatile LbaMail*>(p->h_mail);
     const unsigned long long seq0 = mail_reserve(p, (unsigned long long)std::max(opt->max_iters, 0));
@@ -799,13 +911,21 @@ int plba_lba_visual(plba_problem* p, const plba_lba_options* opt, int K, const d
         hipLaunchKernelGGL(k_lba_landmarks, dim3(nblk), dim3(LM_NT), 0, s, d);
         hipLaunchKernelGGL(k_lba_posesys, dim3(Nkf), dim3(KF_NT), 0, s, d);
         hipLaunchKernelGGL(k_lba_reduce, dim3(1), dim3(256), 0, s, d, nblk, it, seq);
-        HIPCK(p, hipMemsetAsync(sys.p, 0, sysn * 8, s));
-        hipLaunchKernelGGL(k_lba_sysinit, grid(std::max(Nkf * 36, Ppad), 256), dim3(256), 0, s, d);
-        hipLaunchKernelGGL(k_lba_dinv, dim3(nblk), dim3(LM_NT), 0, s, d);
-        if (nchunk) hipLaunchKernelGGL(k_lba_pairs, dim3(nchunk), dim3(64), 0, s, d);
-        hipLaunchKernelGGL(k_lba_rhs, dim3(Nkf), dim3(KF_NT), 0, s, d);
-        launch_cholesky(dd, p->opt.use_mfma != 0, it + 1, s);      // (not gated: after the run has ended it factors the unit padding of a cleared system, at most one pass of it)
-        launch_trsv_back(dd, p->opt.use_mfma != 0, it + 1, s);
+        if (sparse) {
+            hipLaunchKernelGGL(k_lba_dinv, dim3(nblk), dim3(LM_NT), 0, s, dlm);
+            hipLaunchKernelGGL(k_lba_sblk, dim3(nsblk), dim3(64), 0, s, d);
+            hipLaunchKernelGGL(k_lba_rhs, dim3(Nkf), dim3(KF_NT), 0, s, d);
+            pgo_sparse_launch(sd, plan, s);      // (every kernel of it returns at once after the run has ended)
+            hipLaunchKernelGGL(k_lba_smerge, dim3(1), dim3(1), 0, s, d);
+        } else {
+            HIPCK(p, hipMemsetAsync(sys.p, 0, sysn * 8, s));
+            hipLaunchKernelGGL(k_lba_sysinit, grid(std::max(Nkf * 36, Ppad), 256), dim3(256), 0, s, d);
+            hipLaunchKernelGGL(k_lba_dinv, dim3(nblk), dim3(LM_NT), 0, s, dlm);
+            if (nchunk) hipLaunchKernelGGL(k_lba_pairs, dim3(nchunk), dim3(64), 0, s, d);
+            hipLaunchKernelGGL(k_lba_rhs, dim3(Nkf), dim3(KF_NT), 0, s, d);
+            launch_cholesky(dd, p->opt.use_mfma != 0, it + 1, s);      // (not gated: after the run has ended it factors the unit padding of a cleared system, at most one pass of it)
+            launch_trsv_back(dd, p->opt.use_mfma != 0, it + 1, s);
+        }
         hipLaunchKernelGGL(k_lba_backsub, dim3(nblk), dim3(LM_NT), 0, s, d);
         hipLaunchKernelGGL(k_lba_update, grid(std::max<size_t>(nl, Nkf), 256), dim3(256), 0, s, d, nblk);
         hipLaunchKernelGGL(k_lba_post, dim3(1), dim3(1), 0, s, d, it, seq);
@@ -837,6 +957,7 @@ int plba_lba_visual(plba_problem* p, const plba_lba_options* opt, int K, const d
     if (Np) memcpy(xyz3, hXl.data(), (size_t)3 * Np * 8);
     if (Nl) memcpy(pq6, hXl.data() + 3 * (size_t)Np, (size_t)6 * Nl * 8);
     st->iterations = iters; st->updates = updates; st->err_last = err; st->lambda = lambda; st->solver_failed = failed ? 1 : 0;
+    for (int i = 0; i < 8; ++i) p->lba_sparse[i] = srec[i];
     return PLBA_OK;
 }
 

@@ -317,7 +317,8 @@ struct plba_problem {
     int pr_m = 0;                         // dropped dimension of the device-made prior (plba_get_prior)
     plba::MargPending* mp = nullptr;      // the marginalization that makes it, while it may still be in the stream (resolved by its first consumer)
     double pgo_sparse[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // last plba_optimize_pose_graph (plba_debug_get "pgo_sparse", include/plba.h)
-    plba::BowState* bow = nullptr;        // place recognition (plba_bow_*): made by the first plba_bow_set_vocabulary, dropped by plba_bow_discard()
+    double lba_sparse[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // last plba_lba_visual (plba_debug_get "lba_sparse", include/plba.h)
+    plba::BowState* bow = nullptr;       // place recognition (plba_bow_*): made by the first plba_bow_set_vocabulary, dropped by plba_bow_discard()
     long host_waits = 0;                  // times the library blocked the calling thread on the device (plba_debug_get "host_waits")
     plba::Robust rob;
     // shard

@@ -499,6 +499,74 @@ def make_visual_window(K=8, Np=300, Nl=60, n_fixed=2, seed=0x1BA, noise_px=0.5, 
                 truth=dict(T=T_true, xyz=xyz_true, pq=pq_true))
 
 
+def make_map_window(n_local, n_fixed=2, pts_per_kf=20, lns_per_kf=4, track=(2, 6), revisits=3, revisit_gap=(50, 120), seed=0x3A9,
+                    noise_px=0.5, pose_noise=(0.02, 0.01), lm_noise=0.03):
+    """Synthetic input of a whole-map visual BA (MapHandler::globalBundleAdjustment): the arrays of make_visual_window for a long
+    trajectory.  Every keyframe is the first to see `pts_per_kf` points and `lns_per_kf` lines, each tracked over track[0] .. track[1]
+    consecutive keyframes (cycled, so every count is exact) and placed in front of the middle keyframe of its track; `revisits` times
+    two stretches of two keyframes, revisit_gap[0] .. revisit_gap[1] keyframes apart, share four points placed in front of the later
+    one: the long-range links of the covisibility graph."""
+    rng = np.random.default_rng(seed)
+    cam = (FX, FY, CX, CY)
+    fx, fy, cx, cy = cam
+    K = n_local + n_fixed
+    T_true = np.tile(np.eye(4), (K, 1, 1))
+    for k in range(K):
+        # (rotation angles stay in 0.1 .. 0.8 rad however long the trajectory: logmap_se3 as coded loses its digits near 0 and near pi)
+        T_true[k, :3, :3] = exp_so3(np.array([0.02 * np.sin(0.7 * k), 0.05 * np.sin(0.4 * k + 0.3), 0.4 + 0.3 * np.sin(0.013 * k)]))
+        T_true[k, :3, 3] = [0.25 * k, 0.03 * np.sin(k), 0.05 * k]
+
+    def proj(kf, X):     # observation e: X[e] seen from keyframe kf[e]
+        Xc = np.einsum("nji,nj->ni", T_true[kf, :3, :3], X - T_true[kf, :3, 3])
+        return np.stack([cx + fx * Xc[:, 0] / Xc[:, 2], cy + fy * Xc[:, 1] / Xc[:, 2]], -1)
+
+    def cloud(n):
+        return np.stack([rng.uniform(-2.5, 2.5, n), rng.uniform(-1.5, 1.5, n), rng.uniform(4.0, 10.0, n)], -1)
+
+    def tracks(per):
+        out, anchor, q = [], [], 0
+        for k in range(K - 1):
+            for _ in range(per):
+                ln = track[0] + q % (track[1] - track[0] + 1); q += 1
+                ks = list(range(k, min(K, k + ln)))
+                out.append(ks); anchor.append(ks[len(ks) // 2])
+        return out, anchor
+    pt_tracks, pt_anchor = tracks(pts_per_kf)
+    ln_tracks, ln_anchor = tracks(lns_per_kf)
+    for _ in range(revisits if n_local > revisit_gap[0] + 4 else 0):
+        gap = int(rng.integers(revisit_gap[0], min(revisit_gap[1], n_local - 4) + 1))
+        a = n_fixed + int(rng.integers(0, n_local - gap - 1))
+        for _ in range(4):
+            pt_tracks.append([a, a + 1, a + gap, a + gap + 1]); pt_anchor.append(a + gap)
+
+    def place(anchor, local):
+        c = T_true[np.asarray(anchor, int)]
+        return c[:, :3, 3] + np.einsum("nij,nj->ni", c[:, :3, :3], local)
+    xyz_true = place(pt_anchor, cloud(len(pt_tracks)))
+    po_pt = np.repeat(np.arange(len(pt_tracks)), [len(t) for t in pt_tracks]).astype(np.int32)
+    po_kf = np.concatenate(pt_tracks).astype(np.int32)
+    uv = proj(po_kf, xyz_true[po_pt]) + rng.normal(0.0, noise_px, (len(po_pt), 2))
+    P = place(ln_anchor, cloud(len(ln_tracks)))
+    Q = P + np.einsum("nij,nj->ni", T_true[np.asarray(ln_anchor, int)][:, :3, :3],
+                      np.stack([rng.uniform(-1, 1, len(P)), rng.uniform(-1, 1, len(P)), rng.uniform(-0.5, 0.5, len(P))], -1))
+    lo_ln = np.repeat(np.arange(len(ln_tracks)), [len(t) for t in ln_tracks]).astype(np.int32)
+    lo_kf = np.concatenate(ln_tracks).astype(np.int32) if ln_tracks else np.zeros(0, np.int32)
+    one = np.ones((len(lo_ln), 1))
+    a = np.hstack([proj(lo_kf, P[lo_ln]) + rng.normal(0.0, noise_px, (len(lo_ln), 2)), one])
+    b = np.hstack([proj(lo_kf, Q[lo_ln]) + rng.normal(0.0, noise_px, (len(lo_ln), 2)), one])
+    l3 = np.cross(a, b)
+    l3 = l3 / np.hypot(l3[:, 0], l3[:, 1])[:, None]
+    kf_loc = np.array([-1 if k < n_fixed else k - n_fixed for k in range(K)], np.int32)
+    T = T_true.copy()
+    for k in range(n_fixed, K):
+        T[k, :3, :3] = T[k, :3, :3] @ exp_so3(rng.normal(0.0, pose_noise[1], 3))
+        T[k, :3, 3] += rng.normal(0.0, pose_noise[0], 3)
+    pq_true = np.concatenate([P, Q], -1)
+    return dict(cam=cam, T_kf_w=T, kf_loc=kf_loc, xyz=xyz_true + rng.normal(0.0, lm_noise, xyz_true.shape),
+                pq=pq_true + rng.normal(0.0, lm_noise, pq_true.shape), po_pt=po_pt, po_kf=po_kf, uv=uv, lo_ln=lo_ln, lo_kf=lo_kf, l3=l3,
+                truth=dict(T=T_true, xyz=xyz_true, pq=pq_true))
+
+
 # ---------------------------------------------------------------------------------------------
 # consecutive sliding windows of one sequence (plba_slide_window; src/mapHandler.cpp:1178-1221, 4815-4825, 5769-5783)
 # ---------------------------------------------------------------------------------------------
