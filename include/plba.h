@@ -119,7 +119,9 @@ typedef struct {
                                    Jacobi of the marginalization's kept block starts cold, without the tridiagonal pre-rotation;
                                    bit 4 (tests): plba_compute_marginals keeps host copies of its pose system S as it stands before
                                    the factorisation and of the full Sigma_pp, both P x P row-major, for plba_debug_get("cov_S") /
-                                   ("cov_Sigma"); two more blocking copies, the reported covariances keep their bits             (0) */
+                                   ("cov_Sigma"); two more blocking copies, the reported covariances keep their bits;
+                                   bit 5 (tests): plba_pose_graph_marginals keeps a host copy of the 6 x 6 blocks of H as the device
+                                   summed them, for plba_debug_get("pgo_cov_H"); one more blocking copy, same bits            (0) */
     int    pgo_solver;          /* linear solver of plba_optimize_pose_graph: 0 = dense Cholesky of the whole system; 1 = sparse
                                    multifrontal Cholesky (nested dissection, 6 x 6 blocks), for whole-map graphs; any other value:
                                    plba_optimize_pose_graph fails with PLBA_ERR_INVALID                                      (0) */
@@ -129,6 +131,7 @@ typedef struct {
 #define PLBA_DIAG_LEAD_WAIT_FAIL 4
 #define PLBA_DIAG_NO_MARG_PREROTATE 8
 #define PLBA_DIAG_COV_DUMP 16
+#define PLBA_DIAG_PGO_COV_DUMP 32
 
 void plba_default_options(plba_options* o);
 
@@ -537,6 +540,54 @@ typedef struct plba_pose_graph {
 int plba_optimize_pose_graph(plba_problem* p, plba_pose_graph* g, int max_iters, double user_lambda_init, int initial_guess,
                              plba_stats* stats, plba_trace_row* trace, int trace_cap, int* n_trace);
 
+/* ---- marginal covariances of a whole pose graph (g2o computeMarginals on the loop-closure graph) ------------------------
+ * The uncertainty of the graph of plba_optimize_pose_graph at the poses given: per vertex the 6 x 6 block of H^-1, and
+ * Cov(x_i, x_j) for the pairs asked for, taken from the sparse factor.  Nothing of size (6 n)^2 is formed: the cost is of the
+ * order of one factorisation and the memory is that of options.pgo_solver = 1.
+ *  - Linearisation: once, at g->pose12 as given; no initial guess, no optimisation, no damping (lambda = 0).
+ *    H = sum J^T Omega J over the free vertices (those an edge touches that are not fixed), by the kernels
+ *    plba_optimize_pose_graph linearises with.  g is not written.
+ *  - Tangent space: the six coordinates of VertexSE3::oplus as the facade restates it, X <- X fromVectorMQT(x): the local
+ *    translation, then the vector part of the unit quaternion.  The rotation entries are therefore HALF-angles: the
+ *    covariance of a small rotation vector is 4 x the lower right 3 x 3.
+ *  - Method: the multifrontal Cholesky factorisation of the sparse path (nested dissection and symbolic factorisation once
+ *    per call on the host), then Takahashi's selected inversion down the elimination tree, in place in the fronts: it
+ *    yields the entries of H^-1 on the pattern of L, which holds every diagonal block and every block an edge names.
+ *    The call always takes the sparse path, whatever options.pgo_solver says (an invalid value does not matter to it).
+ *  - Vertex status: 0 computed; 1 fixed vertex: zero covariance; 2 no edge touches the vertex (and it is not fixed): it is
+ *    not in the system, NaN covariance.
+ *  - Pair status: 2 if either end has status 2 (NaN); otherwise 1 if either end is fixed (zeros); otherwise 0 if the block
+ *    lies in the pattern of the factor; otherwise 3 (NaN).  Status 0 is guaranteed for i == j and for every pair an edge
+ *    joins.  For any other pair the status follows from the fill of the ordering; it is the same on every call with the
+ *    same graph.  (Blocks outside the pattern need column solves with the factor: not this entry.)
+ *  - Exact properties: a vertex block is exactly symmetric (one triangle is computed and mirrored); pair (i, j) is the
+ *    bitwise transpose of pair (j, i); pair (i, i) equals the vertex block bit for bit.  Two calls give identical bits.
+ *  - Numerical failure: a pivot of the factorisation that is not > 0 or not finite (the sparse solver's own test):
+ *    PLBA_ERR_NUMERIC, no output buffer is written, plba_last_error names the front.  A graph without a fixed vertex has a
+ *    gauge freedom that roundoff may leave at a positive pivot: such a graph has no meaningful covariance and is not
+ *    guaranteed to be caught.
+ *  - Refused with PLBA_ERR_INVALID, outputs untouched: everything plba_optimize_pose_graph refuses about the graph; a
+ *    pair index outside [0, nv); n_pairs < 0; a requested bit without its buffer; want with neither bit set.
+ *  - The problem's state is left alone: the uploaded window is neither read nor written, a following plba_optimize or
+ *    plba_optimize_pose_graph is bit-identical to one without this call in between.  The call blocks once, for the
+ *    read-back of the control block and the results together (plba_debug_get("host_waits") grows by 1; by one more under
+ *    PLBA_DIAG_PGO_COV_DUMP, and by one more when a failed factorisation is run again to name the front).  A plan that fails its own index checks: PLBA_ERR_INTERNAL before anything is launched.
+ *  - plba_debug_get(p, "pgo_cov") (8, at any time) describes the last call, laid out as "pgo_sparse": [0] 1 after a
+ *    successful call, [1] free vertices, [2] fronts, [3] tree levels, [4] nonzero 6 x 6 blocks of L, [5] largest front
+ *    dimension, [6] device bytes the call allocated, [7] host ms of the analysis; all 0 before the first call and after a
+ *    refused or failed one.  Under PLBA_DIAG_PGO_COV_DUMP, plba_debug_get(p, "pgo_cov_H") returns the blocks of H as the
+ *    device summed them: nblk x 36, blocks in ascending (row rank, column rank) with row >= column, free ranks in
+ *    ascending vertex order; empty otherwise. */
+typedef struct plba_pgo_marginals {
+    int            want;         /* bit 0: one block per vertex; bit 1: the pair blocks                          */
+    int            n_pairs;
+    const int32_t* pairs;        /* [n_pairs][2] vertex indices (i, j); any order, repeats and i == j allowed    */
+    double*  v_cov;    uint8_t* v_status;     /* [nv][6][6] row-major, [nv]      (status pointers may be NULL)   */
+    double*  pair_cov; uint8_t* pair_status;  /* [n_pairs][6][6] = Cov(x_i, x_j), [n_pairs]                       */
+    int32_t  n_status[4];        /* out: vertices with status 0, 1, 2; pairs with status 3                      */
+} plba_pgo_marginals;
+int plba_pose_graph_marginals(plba_problem* p, const plba_pose_graph* g, plba_pgo_marginals* m);
+
 /* ---- loop-closure candidate verification: batched relative pose ------------------------------------
  * MapHandler::isLoopClosure's numeric step, computeRelativePoseRobustGN (src/mapHandler.cpp:3675-4066; protocol 0) or the plain
  * computeRelativePoseGN (:3411-3673; protocol 1), for B candidates in ONE launch, one wave per candidate: a Gauss-Newton on one SE(3)
@@ -849,6 +900,7 @@ int  plba_bow_reset(plba_problem* p);
  * system S = Hpp - sum Hpl Hr^-1 Hlp as the device built it, and Sigma_pp = S^-1 as the device formed it, in the pose-side index order;
  * "host_waits" (1, at any time, waits for nothing): how often the library has blocked the calling thread on the device;
  * "pgo_sparse" (8, at any time): the last plba_optimize_pose_graph's solver (see there);
+ * "pgo_cov" (8, at any time), "pgo_cov_H" (nblk * 36 under PLBA_DIAG_PGO_COV_DUMP): the last plba_pose_graph_marginals (see there);
  * "lba_sparse" (8, at any time): the last plba_lba_visual's solver (see there);
  * "bow_db" (5, at any time): the place-recognition database, [keyframes, live keyframes, stored entries of the point vectors, of the
  * line vectors, device bytes held]. */

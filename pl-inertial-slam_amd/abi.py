@@ -84,6 +84,12 @@ class PoseGraph(C.Structure):
                 ("meas12", c_double_p), ("info36", c_double_p)]
 
 
+class PgoMarginals(C.Structure):
+    """plba_pgo_marginals of include/plba.h"""
+    _fields_ = [("want", C.c_int), ("n_pairs", C.c_int), ("pairs", c_int32_p), ("v_cov", c_double_p), ("v_status", c_uint8_p),
+                ("pair_cov", c_double_p), ("pair_status", c_uint8_p), ("n_status", C.c_int32 * 4)]
+
+
 class RefineOptions(C.Structure):
     """plba_refine_options of include/plba.h"""
     _fields_ = [("max_iters", C.c_int), ("max_trials", C.c_int), ("lambda_init", C.c_double), ("select_point", c_uint8_p), ("select_line", c_uint8_p),
@@ -175,8 +181,9 @@ _P = C.c_void_p  # plba_problem*
 # pose graph as orc_pgo, a checker entry of its own outside this table.  refine_landmarks: g2o's structure-only solver is a stub at the
 # reference's boundary; its checker is the numpy restatement tests/refine_ref.py.  relative_pose: its checker is tests/relpose_ref.py.
 # track_pose: its checker is tests/track_ref.py.  match_descriptors, verify_loop_candidates: their checker is tests/match_ref.py.
-# bow_*: their checker is tests/bow_ref.py)
+# bow_*: their checker is tests/bow_ref.py.  pose_graph_marginals: the reference computes none; its checker is tests/pgo_cov_ref.py)
 PRODUCT_ONLY = {"slide_window", "get_sizes", "marginalize_to_prior", "get_prior", "compute_marginals", "optimize_pose_graph",
+                "pose_graph_marginals",
                 "refine_default_options", "refine_landmarks", "relpose_default_options", "relative_pose", "track_default_options", "track_pose",
                 "match_default_options", "match_descriptors", "loop_default_options", "verify_loop_candidates",
                 "bow_default_options", "bow_set_vocabulary", "bow_transform", "bow_insert_keyframes", "bow_remove_keyframe", "bow_reset"}
@@ -254,6 +261,7 @@ SIGNATURES = {
     "bow_remove_keyframe": (C.c_int, [_P, C.c_int]),
     "bow_reset": (C.c_int, [_P]),
     "optimize_pose_graph": (C.c_int, [_P, C.POINTER(PoseGraph), C.c_int, C.c_double, C.c_int, C.POINTER(Stats), C.POINTER(TraceRow), C.c_int, C.POINTER(C.c_int)]),
+    "pose_graph_marginals": (C.c_int, [_P, C.POINTER(PoseGraph), C.POINTER(PgoMarginals)]),
 }
 
 
@@ -723,6 +731,38 @@ class Problem:
         trace = [dict(iteration=r.iteration, trial=r.trial, accepted=r.accepted, solver_ok=r.solver_ok, lam=r.lam, chi2_current=r.chi2_current,
                       chi2_trial=r.chi2_trial, scale=r.scale, rho=r.rho) for r in rows[:min(ntr.value, cap)]]
         return X, stats, trace
+
+    def pgo_marginals(self, pose12, ei, ej, meas12, info=None, fixed=None, pairs=None):
+        """plba_pose_graph_marginals: the 6 x 6 marginal covariance of every vertex of the pose graph at pose12 and Cov(x_i, x_j) of the
+        pairs (n, 2) given, from the sparse factor.  Arguments as pgo().  Returns dict(v_cov (nv, 6, 6), v_status (nv,), pair_cov (n, 6, 6),
+        pair_status (n,), n_status (4,)); the problem's window is not touched."""
+        X = _f64(pose12)
+        if X.ndim != 2 or X.shape[1] != 12 or X.shape[0] < 1:
+            raise ValueError("pose12 must be (nv, 12), nv >= 1")
+        nv = X.shape[0]
+        ei, ej = _i32(np.asarray(ei).ravel()), _i32(np.asarray(ej).ravel())
+        Z = _f64(meas12)
+        ne = len(ei)
+        if len(ej) != ne or Z.size != 12 * ne:
+            raise ValueError("ei, ej and meas12 must describe the same %d edges" % ne)
+        Z = Z.reshape(ne, 12)
+        om = None if info is None else _f64(info).reshape(-1)
+        if om is not None and om.size != 36 * ne:
+            raise ValueError("info must be (ne, 6, 6)")
+        fx = None if fixed is None else _u8(np.asarray(fixed).astype(bool))
+        if fx is not None and fx.size != nv:
+            raise ValueError("fixed must have nv entries")
+        g = PoseGraph(nv, _dp(X), _up(fx), ne, _ip(ei), _ip(ej), _dp(Z), _dp(om))
+        pr = np.zeros((0, 2), np.int32) if pairs is None else np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+        vc = np.zeros((nv, 6, 6)); vs = np.zeros(nv, np.uint8)
+        pc = np.zeros((max(len(pr), 1), 6, 6)); ps = np.zeros(max(len(pr), 1), np.uint8)
+        m = PgoMarginals()
+        m.want = 1 | (2 if len(pr) else 0)
+        m.n_pairs = len(pr)
+        m.pairs = _ip(pr) if len(pr) else None
+        m.v_cov, m.v_status, m.pair_cov, m.pair_status = _dp(vc), _up(vs), _dp(pc), _up(ps)
+        self.call("pose_graph_marginals", C.byref(g), C.byref(m))
+        return dict(v_cov=vc, v_status=vs, pair_cov=pc[:len(pr)], pair_status=ps[:len(pr)], n_status=np.array(list(m.n_status), np.int32))
 
     def refine_landmarks(self, select_point=None, select_line=None, **opts):
         """plba_refine_landmarks: every selected landmark fitted to the keyframes the device holds (structure-only LM, one launch).

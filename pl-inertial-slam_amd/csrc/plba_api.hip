@@ -55,6 +55,8 @@ static void reset_for_reuse(plba_problem* p, const plba_options* opt) {
     p->prior_dev = false; p->prior_changed = false; p->pr_m = 0; p->host_waits = 0;
     for (double& v : p->pgo_sparse) v = 0.0;
     for (double& v : p->lba_sparse) v = 0.0;
+    for (double& v : p->pgo_cov) v = 0.0;
+    p->pgo_cov_H.clear();
     memset(&p->rob, 0, sizeof p->rob);
     p->rank = 0; p->world = 1; p->xfn = nullptr; p->xuser = nullptr;
     p->dirty = true; p->P = p->Ppad = p->ld = p->L = p->E = 0; p->cur = 0;
@@ -2667,6 +2669,16 @@ int plba_debug_get(plba_problem* p, const char* what, double* out, size_t cap, s
     if (w == "pgo_sparse") {      // (host-side record of the last plba_optimize_pose_graph: the pose graph uploads no window)
         if (n) *n = 8;
         for (size_t i = 0; out && i < cap && i < 8; ++i) out[i] = p->pgo_sparse[i];
+        return PLBA_OK;
+    }
+    if (w == "pgo_cov") {         // (host-side record of the last plba_pose_graph_marginals)
+        if (n) *n = 8;
+        for (size_t i = 0; out && i < cap && i < 8; ++i) out[i] = p->pgo_cov[i];
+        return PLBA_OK;
+    }
+    if (w == "pgo_cov_H") {       // (its Hblk, kept under PLBA_DIAG_PGO_COV_DUMP; empty otherwise)
+        if (n) *n = p->pgo_cov_H.size();
+        for (size_t i = 0; out && i < cap && i < p->pgo_cov_H.size(); ++i) out[i] = p->pgo_cov_H[i];
         return PLBA_OK;
     }
     if (w == "lba_sparse") {      // (host-side record of the last plba_lba_visual)

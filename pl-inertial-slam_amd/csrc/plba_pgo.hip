@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "plba_internal.h"
+#include "plba_pgo_cov.h"
 #include "plba_pgo_sparse.h"
 #include "plba_problem.h"
 
@@ -381,6 +382,11 @@ __global__ __launch_bounds__(256) void k_pgo_chi_only(PgoDev d) {
     if (threadIdx.x == 0) { d.ctl->chi2_initial = chi; d.ctl->chi2_final = chi; }
 }
 
+// plba_pose_graph_marginals, after a failed factorisation: behind a launch of k_sps_factor, notes the first tag at which solver_ok is 0
+__global__ void k_pgo_cov_mark(const Ctrl* c, int* rec, int tag) {
+    if (!c->solver_ok && *rec < 0) *rec = tag;
+}
+
 struct HIso { double R[9], t[3]; };
 HIso h_load(const double* p) { HIso a; memcpy(a.R, p, 72); memcpy(a.t, p + 9, 24); return a; }
 void h_store(const HIso& a, double* p) { memcpy(p, a.R, 72); memcpy(p + 9, a.t, 24); }
@@ -398,6 +404,66 @@ HIso h_inv(const HIso& a) {
     const V3 x = mul(Rt, v3(a.t[0], a.t[1], a.t[2]));
     HIso r; memcpy(r.R, Rt.a, 72); r.t[0] = -x.x; r.t[1] = -x.y; r.t[2] = -x.z;
     return r;
+}
+
+// What both pose-graph entry points build from the graph on the host: the checks of the graph, the free ranks (the vertices an edge
+// touches that are not fixed, in ascending vertex order) and, when asked for, every nonzero 6 x 6 block of H (row rank >= column rank,
+// ascending) with its (edge, slot) sources in edge order.  dense_map: blkmap too, for the dense solver's fill.
+struct PgoGraphSetup {
+    int n = 0;                                        // free vertices
+    std::vector<int32_t> fr, free_v;                  // free rank of each vertex (-1: fixed or untouched), vertex of each free rank
+    std::vector<int32_t> blk_start, blk_src, blk_diag, blk_row, blk_col, dg_blk, blkmap;
+};
+int pgo_graph_setup(plba_problem* p, const plba_pose_graph* g, const char* who, bool want_blocks, bool dense_map, PgoGraphSetup& u) {
+    const int nv = g->nv, ne = g->ne;
+    if (nv <= 0 || ne < 0) FAIL(p, PLBA_ERR_INVALID, "%s: nv = %d, ne = %d", who, nv, ne);
+    if (!g->pose12 || (ne > 0 && (!g->ei || !g->ej || !g->meas12))) FAIL(p, PLBA_ERR_INVALID, "%s: missing array", who);
+    for (size_t i = 0; i < (size_t)12 * nv; ++i)
+        if (!std::isfinite(g->pose12[i])) FAIL(p, PLBA_ERR_INVALID, "%s: pose of vertex %d is not finite", who, (int)(i / 12));
+    for (int k = 0; k < ne; ++k) {
+        if (g->ei[k] < 0 || g->ei[k] >= nv || g->ej[k] < 0 || g->ej[k] >= nv) FAIL(p, PLBA_ERR_INVALID, "%s: edge %d names a vertex out of range", who, k);
+        if (g->ei[k] == g->ej[k]) FAIL(p, PLBA_ERR_INVALID, "%s: edge %d joins vertex %d to itself", who, k, g->ei[k]);
+        for (int i = 0; i < 12; ++i) if (!std::isfinite(g->meas12[(size_t)12 * k + i])) FAIL(p, PLBA_ERR_INVALID, "%s: measurement of edge %d is not finite", who, k);
+        if (g->info36) for (int i = 0; i < 36; ++i) if (!std::isfinite(g->info36[(size_t)36 * k + i])) FAIL(p, PLBA_ERR_INVALID, "%s: information of edge %d is not finite", who, k);
+    }
+    std::vector<int32_t>& fr = u.fr; std::vector<int32_t>& free_v = u.free_v;
+    fr.assign(nv, -1); free_v.clear();
+    {
+        std::vector<char> touched(nv, 0);
+        for (int k = 0; k < ne; ++k) { touched[g->ei[k]] = 1; touched[g->ej[k]] = 1; }
+        for (int v = 0; v < nv; ++v) if (touched[v] && !(g->fixed && g->fixed[v] != 0)) { fr[v] = (int32_t)free_v.size(); free_v.push_back(v); }
+    }
+    const int n = u.n = (int)free_v.size();
+    std::vector<int32_t>&blk_start = u.blk_start, &blk_src = u.blk_src, &blk_diag = u.blk_diag, &blk_row = u.blk_row, &blk_col = u.blk_col, &dg_blk = u.dg_blk, &blkmap = u.blkmap;
+    blk_start.clear(); blk_src.clear(); blk_diag.clear(); blk_row.clear(); blk_col.clear(); dg_blk.clear(); blkmap.clear();
+    if (want_blocks && n > 0) {
+        struct Src { int32_t r, c, src; };
+        std::vector<Src> s;
+        s.reserve((size_t)3 * ne);
+        for (int k = 0; k < ne; ++k) {
+            const int a = fr[g->ei[k]], b = fr[g->ej[k]];
+            if (a >= 0) s.push_back({a, a, 4 * k + 0});
+            if (b >= 0) s.push_back({b, b, 4 * k + 1});
+            if (a >= 0 && b >= 0) { if (b > a) s.push_back({b, a, 4 * k + 2}); else s.push_back({a, b, 4 * k + 3}); }
+        }
+        std::stable_sort(s.begin(), s.end(), [](const Src& x, const Src& y) { return x.r != y.r ? x.r < y.r : x.c < y.c; });   // edge order within a block
+        if (dense_map) blkmap.assign((size_t)n * n, -1);
+        dg_blk.assign(n, -1);
+        for (size_t i = 0; i < s.size(); ++i) {
+            if (i == 0 || s[i].r != s[i - 1].r || s[i].c != s[i - 1].c) {
+                const int id = (int)blk_row.size();
+                blk_start.push_back((int32_t)i); blk_row.push_back(s[i].r); blk_col.push_back(s[i].c); blk_diag.push_back(s[i].r == s[i].c ? 1 : 0);
+                if (dense_map) {
+                    blkmap[(size_t)s[i].r * n + s[i].c] = 2 * id;
+                    if (s[i].r != s[i].c) blkmap[(size_t)s[i].c * n + s[i].r] = 2 * id + 1;
+                }
+                if (s[i].r == s[i].c) dg_blk[s[i].r] = id;
+            }
+            blk_src.push_back(s[i].src);
+        }
+        blk_start.push_back((int32_t)s.size());
+    }
+    return PLBA_OK;
 }
 
 }  // namespace
@@ -418,16 +484,8 @@ int plba_optimize_pose_graph(plba_problem* p, plba_pose_graph* g, int max_iters,
     if (p->opt.pgo_solver != 0 && p->opt.pgo_solver != 1) FAIL(p, PLBA_ERR_INVALID, "plba_optimize_pose_graph: options.pgo_solver = %d", p->opt.pgo_solver);
     if (!std::isfinite(user_lambda_init)) FAIL(p, PLBA_ERR_INVALID, "plba_optimize_pose_graph: user_lambda_init is not finite");
     const int nv = g->nv, ne = g->ne;
-    if (nv <= 0 || ne < 0) FAIL(p, PLBA_ERR_INVALID, "plba_optimize_pose_graph: nv = %d, ne = %d", nv, ne);
-    if (!g->pose12 || (ne > 0 && (!g->ei || !g->ej || !g->meas12))) FAIL(p, PLBA_ERR_INVALID, "plba_optimize_pose_graph: missing array");
-    for (size_t i = 0; i < (size_t)12 * nv; ++i)
-        if (!std::isfinite(g->pose12[i])) FAIL(p, PLBA_ERR_INVALID, "plba_optimize_pose_graph: pose of vertex %d is not finite", (int)(i / 12));
-    for (int k = 0; k < ne; ++k) {
-        if (g->ei[k] < 0 || g->ei[k] >= nv || g->ej[k] < 0 || g->ej[k] >= nv) FAIL(p, PLBA_ERR_INVALID, "plba_optimize_pose_graph: edge %d names a vertex out of range", k);
-        if (g->ei[k] == g->ej[k]) FAIL(p, PLBA_ERR_INVALID, "plba_optimize_pose_graph: edge %d joins vertex %d to itself", k, g->ei[k]);
-        for (int i = 0; i < 12; ++i) if (!std::isfinite(g->meas12[(size_t)12 * k + i])) FAIL(p, PLBA_ERR_INVALID, "plba_optimize_pose_graph: measurement of edge %d is not finite", k);
-        if (g->info36) for (int i = 0; i < 36; ++i) if (!std::isfinite(g->info36[(size_t)36 * k + i])) FAIL(p, PLBA_ERR_INVALID, "plba_optimize_pose_graph: information of edge %d is not finite", k);
-    }
+    PgoGraphSetup gs;
+    if (int rc = pgo_graph_setup(p, g, "plba_optimize_pose_graph", max_iters > 0, p->opt.pgo_solver != 1, gs)) return rc;
     auto is_fixed = [&](int v) { return g->fixed && g->fixed[v] != 0; };
 
     // ---- host: estimates, initial guess, active set, block structure --------------------------------------------------------------
@@ -456,42 +514,10 @@ int plba_optimize_pose_graph(plba_problem* p, plba_pose_graph* g, int max_iters,
             front.swap(next);
         }
     }
-    std::vector<int32_t> fr(nv, -1), free_v;
-    {
-        std::vector<char> touched(nv, 0);
-        for (int k = 0; k < ne; ++k) { touched[g->ei[k]] = 1; touched[g->ej[k]] = 1; }
-        for (int v = 0; v < nv; ++v) if (touched[v] && !is_fixed(v)) { fr[v] = (int32_t)free_v.size(); free_v.push_back(v); }
-    }
-    const int n = (int)free_v.size(), P = 6 * n;
+    std::vector<int32_t>& free_v = gs.free_v;
+    const int n = gs.n, P = 6 * n;
     const bool run = max_iters > 0 && n > 0, sparse = p->opt.pgo_solver == 1;
-    std::vector<int32_t> blk_start, blk_src, blk_diag, blk_row, blk_col, dg_blk, blkmap;
-    if (run) {
-        struct Src { int32_t r, c, src; };
-        std::vector<Src> s;
-        s.reserve((size_t)3 * ne);
-        for (int k = 0; k < ne; ++k) {
-            const int a = fr[g->ei[k]], b = fr[g->ej[k]];
-            if (a >= 0) s.push_back({a, a, 4 * k + 0});
-            if (b >= 0) s.push_back({b, b, 4 * k + 1});
-            if (a >= 0 && b >= 0) { if (b > a) s.push_back({b, a, 4 * k + 2}); else s.push_back({a, b, 4 * k + 3}); }
-        }
-        std::stable_sort(s.begin(), s.end(), [](const Src& x, const Src& y) { return x.r != y.r ? x.r < y.r : x.c < y.c; });   // edge order within a block
-        if (!sparse) blkmap.assign((size_t)n * n, -1);
-        dg_blk.assign(n, -1);
-        for (size_t i = 0; i < s.size(); ++i) {
-            if (i == 0 || s[i].r != s[i - 1].r || s[i].c != s[i - 1].c) {
-                const int id = (int)blk_row.size();
-                blk_start.push_back((int32_t)i); blk_row.push_back(s[i].r); blk_col.push_back(s[i].c); blk_diag.push_back(s[i].r == s[i].c ? 1 : 0);
-                if (!sparse) {
-                    blkmap[(size_t)s[i].r * n + s[i].c] = 2 * id;
-                    if (s[i].r != s[i].c) blkmap[(size_t)s[i].c * n + s[i].r] = 2 * id + 1;
-                }
-                if (s[i].r == s[i].c) dg_blk[s[i].r] = id;
-            }
-            blk_src.push_back(s[i].src);
-        }
-        blk_start.push_back((int32_t)s.size());
-    }
+    std::vector<int32_t>&blk_start = gs.blk_start, &blk_src = gs.blk_src, &blk_diag = gs.blk_diag, &blk_row = gs.blk_row, &blk_col = gs.blk_col, &dg_blk = gs.dg_blk, &blkmap = gs.blkmap;
     const int nblk = (int)blk_row.size();
     PgoSparsePlan plan;
     if (sparse) {
@@ -615,6 +641,181 @@ int plba_optimize_pose_graph(plba_problem* p, plba_pose_graph* g, int max_iters,
     out->chi2_initial = cend.chi2_initial; out->chi2_final = cend.chi2_final; out->lambda_final = cend.lambda_final;
     out->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (n_trace) *n_trace = cend.n_trace;
+    return PLBA_OK;
+}
+
+// Marginal covariances of the graph at g->pose12 (include/plba.h): one linearisation by the kernels above, the multifrontal
+// factorisation of plba_pgo_sparse.hip at lambda = 0, the selected inversion of plba_pgo_cov.hip, one read-back.
+int plba_pose_graph_marginals(plba_problem* p, const plba_pose_graph* g, plba_pgo_marginals* m) {
+    if (!p) return PLBA_ERR_INVALID;
+    static const char who[] = "plba_pose_graph_marginals";
+    for (double& v : p->pgo_cov) v = 0.0;      // (a refused or failed call leaves an all-zero record)
+    p->pgo_cov_H.clear();
+    if (!g || !m) FAIL(p, PLBA_ERR_INVALID, "%s: no graph or no request", who);
+    const bool want_v = (m->want & 1) != 0, want_p = (m->want & 2) != 0;
+    if (!want_v && !want_p) FAIL(p, PLBA_ERR_INVALID, "%s: want = %d asks for nothing", who, m->want);
+    if (m->n_pairs < 0) FAIL(p, PLBA_ERR_INVALID, "%s: n_pairs = %d", who, m->n_pairs);
+    if ((want_v && !m->v_cov) || (want_p && (!m->pair_cov || (m->n_pairs > 0 && !m->pairs)))) FAIL(p, PLBA_ERR_INVALID, "%s: a requested bit without its buffer", who);
+    PgoGraphSetup gs;
+    if (int rc = pgo_graph_setup(p, g, who, true, false, gs)) return rc;
+    const int nv = g->nv, ne = g->ne, n = gs.n, P = 6 * n, npairs = want_p ? m->n_pairs : 0;
+    for (int k = 0; k < npairs; ++k)
+        if (m->pairs[2 * k] < 0 || m->pairs[2 * k] >= nv || m->pairs[2 * k + 1] < 0 || m->pairs[2 * k + 1] >= nv) FAIL(p, PLBA_ERR_INVALID, "%s: pair %d names a vertex out of range", who, k);
+    const int nblk = (int)gs.blk_row.size();
+
+    // ---- host: the plan, the statuses and the places of the requested blocks --------------------------------------------------------
+    PgoSparsePlan plan;
+    PgoCovPlan cp;
+    double ms_analysis = 0.0;
+    if (n > 0) {
+        const auto ta = std::chrono::steady_clock::now();
+        if (!pgo_sparse_analyse(n, gs.blk_row, gs.blk_col, plan) || !pgo_cov_prepare(plan, cp)) FAIL(p, PLBA_ERR_INTERNAL, "%s: the sparse analysis failed its checks", who);
+        ms_analysis = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ta).count();
+    }
+    auto vstat = [&](int v) -> uint8_t { return gs.fr[v] >= 0 ? 0 : (g->fixed && g->fixed[v] != 0) ? 1 : 2; };
+    const int n_items = (want_v ? nv : 0) + npairs;
+    std::vector<uint8_t> status((size_t)std::max(n_items, 1), 0);
+    std::vector<PgoCovPlace> places((size_t)std::max(n_items, 1), PgoCovPlace{-1, 0, 0, 0});
+    std::vector<int32_t> ranks((size_t)2 * places.size(), 0);
+    int32_t n_status[4] = {0, 0, 0, 0};
+    for (int v = 0; v < nv; ++v) ++n_status[vstat(v)];
+    {
+        size_t it = 0;
+        if (want_v)
+            for (int v = 0; v < nv; ++v, ++it) {
+                status[it] = vstat(v);
+                if (!status[it]) { places[it] = pgo_cov_locate(plan, cp, gs.fr[v], gs.fr[v]); ranks[2 * it] = ranks[2 * it + 1] = gs.fr[v]; }
+            }
+        for (int k = 0; k < npairs; ++k, ++it) {
+            const int i = m->pairs[2 * k], j = m->pairs[2 * k + 1];
+            const uint8_t si = vstat(i), sj = vstat(j);
+            if (si == 2 || sj == 2) status[it] = 2;
+            else if (si == 1 || sj == 1) status[it] = 1;
+            else {
+                places[it] = pgo_cov_locate(plan, cp, gs.fr[i], gs.fr[j]);
+                ranks[2 * it] = gs.fr[i]; ranks[2 * it + 1] = gs.fr[j];
+                if (places[it].front < 0) { status[it] = 3; ++n_status[3]; }
+            }
+        }
+    }
+    if (n > 0 && !pgo_cov_check(plan, cp, places, ranks)) FAIL(p, PLBA_ERR_INTERNAL, "%s: the plan of the selected inversion failed its index checks", who);
+
+    // ---- device ------------------------------------------------------------------------------------------------------------------
+    HIPCK(p, hipSetDevice(p->device));
+    hipStream_t s = p->stream;
+    std::vector<double> X(g->pose12, g->pose12 + (size_t)12 * nv);
+    std::vector<double> Zi((size_t)12 * std::max(ne, 1), 0.0), info((size_t)36 * std::max(ne, 1), 0.0);
+    for (int k = 0; k < ne; ++k) {
+        h_store(h_inv(h_load(g->meas12 + (size_t)12 * k)), &Zi[(size_t)12 * k]);
+        if (g->info36) memcpy(&info[(size_t)36 * k], g->info36 + (size_t)36 * k, 36 * 8);
+        else for (int i = 0; i < 6; ++i) info[(size_t)36 * k + 7 * i] = 1.0;
+    }
+    std::vector<int32_t> hei(g->ei ? g->ei : nullptr, g->ei ? g->ei + ne : nullptr), hej(g->ej ? g->ej : nullptr, g->ej ? g->ej + ne : nullptr);
+    if (hei.empty()) { hei.assign(1, 0); hej.assign(1, 0); }
+    auto nz = [](std::vector<int32_t>& v) { if (v.empty()) v.assign(1, 0); };
+    nz(gs.blk_start); nz(gs.blk_src); nz(gs.blk_diag); nz(gs.blk_row);
+    std::vector<int32_t> hplace((size_t)4 * places.size());
+    for (size_t i = 0; i < places.size(); ++i) { hplace[4 * i] = places[i].front; hplace[4 * i + 1] = places[i].rpos; hplace[4 * i + 2] = places[i].cpos; hplace[4 * i + 3] = places[i].transposed; }
+    DArr<double> dX, dZi, dInfo, dErec, dEchi, dHblk, db, sp_F, sp_R, dG, dOut;
+    DArr<int32_t> dei, dej, dbs, dbsrc, dbdiag, dbrow, dplace, dpar;
+    DArr<int32_t> sp_m, sp_np, sp_row0, sp_rows, sp_umap, sp_chs, sp_ch, sp_ass, sp_as, sp_lv;
+    DArr<long long> sp_off, sp_roff, dgoff;
+    DArr<uint8_t> dstatus;
+    DArr<PgoCtl> dctl;
+    DArr<int> drec;
+    constexpr size_t HEAD = 32;      // doubles in front of the results: the control block as it stands behind the last launch
+    static_assert(sizeof(PgoCtl) <= HEAD * sizeof(double), "the control block fits the head of the read-back");
+    PgoCtl c0; memset(&c0, 0, sizeof c0);
+    c0.lin = 1; c0.c.solver_ok = 1;      // (lambda = 0: no damping)
+    std::vector<PgoCtl> hc0(1, c0);
+    std::vector<int> hrec(1, -1);
+    {
+        // (no wait behind the uploads: the host vectors above live until the read-back below, the call's one blocking wait, has drained the stream)
+        DArrStreamScope staged(s, p->have_ctx ? p->ctx.stage : nullptr);
+        HIPCK(p, dctl.upload(hc0)); HIPCK(p, drec.upload(hrec)); HIPCK(p, dplace.upload(hplace)); HIPCK(p, dstatus.upload(status));
+        HIPCK(p, dOut.alloc(HEAD + (size_t)36 * std::max(n_items, 1), false));
+        if (n > 0) {
+            HIPCK(p, dX.upload(X)); HIPCK(p, dZi.upload(Zi)); HIPCK(p, dInfo.upload(info)); HIPCK(p, dei.upload(hei)); HIPCK(p, dej.upload(hej));
+            HIPCK(p, dEchi.alloc(std::max(ne, 1))); HIPCK(p, dErec.alloc((size_t)PGO_REC * std::max(ne, 1)));
+            HIPCK(p, dbs.upload(gs.blk_start)); HIPCK(p, dbsrc.upload(gs.blk_src)); HIPCK(p, dbdiag.upload(gs.blk_diag)); HIPCK(p, dbrow.upload(gs.blk_row));
+            HIPCK(p, dHblk.alloc((size_t)36 * std::max(nblk, 1))); HIPCK(p, db.alloc(P));
+            HIPCK(p, sp_m.upload(plan.f_m)); HIPCK(p, sp_np.upload(plan.f_np)); HIPCK(p, sp_row0.upload(plan.f_row0)); HIPCK(p, sp_rows.upload(plan.rows));
+            HIPCK(p, sp_umap.upload(plan.umap)); HIPCK(p, sp_chs.upload(plan.ch_start)); HIPCK(p, sp_ass.upload(plan.as_start)); HIPCK(p, sp_as.upload(plan.as));
+            HIPCK(p, sp_lv.upload(plan.lv)); HIPCK(p, sp_off.upload(plan.f_off)); HIPCK(p, sp_roff.upload(plan.f_roff));
+            if (plan.ch.empty()) plan.ch.assign(1, 0);
+            HIPCK(p, sp_ch.upload(plan.ch)); HIPCK(p, sp_F.alloc((size_t)plan.fsize, false)); HIPCK(p, sp_R.alloc((size_t)plan.rsize, false));
+            HIPCK(p, dpar.upload(cp.parent)); HIPCK(p, dgoff.upload(cp.g_off)); HIPCK(p, dG.alloc((size_t)cp.gsize, false));
+        }
+    }
+    PgoDev d; memset(&d, 0, sizeof d);
+    d.nv = nv; d.ne = ne; d.n = n; d.P = P; d.nblk = nblk;
+    d.X = dX.p; d.ei = dei.p; d.ej = dej.p; d.Zi = dZi.p; d.info = dInfo.p; d.erec = dErec.p; d.echi = dEchi.p;
+    d.blk_start = dbs.p; d.blk_src = dbsrc.p; d.blk_diag = dbdiag.p; d.blk_row = dbrow.p; d.Hblk = dHblk.p; d.b = db.p; d.ctl = dctl.p;
+    PgoSparseDev sd; memset(&sd, 0, sizeof sd);
+    sd.f_m = sp_m.p; sd.f_np = sp_np.p; sd.f_row0 = sp_row0.p; sd.rows = sp_rows.p; sd.umap = sp_umap.p; sd.ch_start = sp_chs.p; sd.ch = sp_ch.p;
+    sd.as_start = sp_ass.p; sd.as = sp_as.p; sd.lv = sp_lv.p; sd.f_off = sp_off.p; sd.f_roff = sp_roff.p; sd.F = sp_F.p; sd.R = sp_R.p;
+    sd.Hblk = dHblk.p; sd.b = db.p; sd.c = &dctl.p->c; sd.done = &dctl.p->done;
+    PgoCovDev cd; memset(&cd, 0, sizeof cd);
+    cd.parent = dpar.p; cd.g_off = dgoff.p; cd.G = dG.p; cd.n_items = n_items; cd.place = dplace.p; cd.status = dstatus.p; cd.out = dOut.p + HEAD;
+    size_t bytes = 0;
+    {
+        auto add = [&](const auto& a) { bytes += a.n * sizeof(*a.p); };
+        add(dX); add(dZi); add(dInfo); add(dErec); add(dEchi); add(dHblk); add(db); add(sp_F); add(sp_R); add(dG); add(dOut); add(dei); add(dej); add(dbs);
+        add(dbsrc); add(dbdiag); add(dbrow); add(dplace); add(dpar); add(sp_m); add(sp_np); add(sp_row0); add(sp_rows); add(sp_umap); add(sp_chs); add(sp_ch);
+        add(sp_ass); add(sp_as); add(sp_lv); add(sp_off); add(sp_roff); add(dgoff); add(dstatus); add(dctl); add(drec);
+    }
+    if (n > 0) {
+        hipLaunchKernelGGL(k_pgo_edges<true>, dim3((unsigned)((std::max(ne, 1) + 63) / 64)), dim3(64), 0, s, d);
+        hipLaunchKernelGGL(k_pgo_sum, dim3((unsigned)((std::max(nblk, 1) + 3) / 4)), dim3(256), 0, s, d);
+        pgo_sparse_launch_assemble(sd, plan, s);
+        for (int l = 0; l < plan.nlev; ++l) pgo_sparse_launch_factor(sd, plan.lv_start[l], plan.lv_start[l + 1] - plan.lv_start[l], s);
+    }
+    pgo_cov_launch(sd, cd, plan, s);      // (nothing to invert without a free vertex: the zeros and NaNs of the statuses alone)
+    HIPCK(p, hipMemcpyAsync(dOut.p, dctl.p, sizeof(PgoCtl), hipMemcpyDeviceToDevice, s));
+    HIPCK(p, hipGetLastError());
+    // the one read-back: control block and results together, into host memory; the caller's buffers only after the verdict
+    std::vector<double> hall(HEAD + (size_t)36 * std::max(n_items, 1));
+    HIPCK(p, plba_d2h(p, hall.data(), dOut.p, hall.size() * 8));
+    PgoCtl cend;
+    memcpy(&cend, hall.data(), sizeof cend);
+    const double* hout = hall.data() + HEAD;
+    if (!cend.c.solver_ok) {
+        // which front (failure path only): assembled again and factored one front per launch in the order of the levels, in the same
+        // arithmetic (a front reads its children alone), with a one-thread note of the first launch behind which solver_ok is 0
+        int ef = -1;
+        pgo_sparse_launch_assemble(sd, plan, s);
+        for (int e = 0; e < plan.nfront; ++e) {
+            pgo_sparse_launch_factor(sd, e, 1, s);
+            hipLaunchKernelGGL(k_pgo_cov_mark, dim3(1), dim3(1), 0, s, &dctl.p->c, drec.p, e);
+        }
+        HIPCK(p, hipGetLastError());
+        HIPCK(p, plba_d2h(p, &ef, drec.p, sizeof ef));
+        if (ef >= 0 && ef < plan.nfront) {
+            const int f = plan.lv[ef], npv = plan.f_np[f] / 6;
+            const int32_t* rw = plan.rows.data() + plan.f_row0[f];
+            FAIL(p, PLBA_ERR_NUMERIC, "%s: a pivot of the factorisation is not > 0 or not finite in front %d of %d (level %d of %d, dimension %d, %d pivot vertices %d .. %d)",
+                 who, f, plan.nfront, cp.level[f], plan.nlev, plan.f_m[f], npv, gs.free_v[rw[0]], gs.free_v[rw[npv - 1]]);
+        }
+        FAIL(p, PLBA_ERR_NUMERIC, "%s: a pivot of the factorisation is not > 0 or not finite (front not identified)", who);
+    }
+    if ((p->opt.diag & PLBA_DIAG_PGO_COV_DUMP) && n > 0) {      // host copy for plba_debug_get("pgo_cov_H"): read only, the launches are the same
+        p->pgo_cov_H.resize((size_t)36 * nblk);
+        HIPCK(p, plba_d2h(p, p->pgo_cov_H.data(), dHblk.p, p->pgo_cov_H.size() * 8));
+    }
+    // ---- every check has passed: the caller's buffers -----------------------------------------------------------------------------
+    size_t it0 = 0;
+    if (want_v) {
+        memcpy(m->v_cov, hout, (size_t)36 * nv * 8);
+        if (m->v_status) memcpy(m->v_status, status.data(), (size_t)nv);
+        it0 = (size_t)nv;
+    }
+    if (want_p && npairs > 0) {
+        memcpy(m->pair_cov, hout + 36 * it0, (size_t)36 * npairs * 8);
+        if (m->pair_status) memcpy(m->pair_status, status.data() + it0, (size_t)npairs);
+    }
+    for (int i = 0; i < 4; ++i) m->n_status[i] = n_status[i];
+    p->pgo_cov[0] = 1.0; p->pgo_cov[1] = n; p->pgo_cov[2] = plan.nfront; p->pgo_cov[3] = plan.nlev; p->pgo_cov[4] = (double)plan.nnz_blk; p->pgo_cov[5] = plan.max_m;
+    p->pgo_cov[6] = (double)bytes; p->pgo_cov[7] = ms_analysis;
     return PLBA_OK;
 }
 

@@ -54,6 +54,10 @@ struct PgoSparseDev {
 };
 #ifdef __HIPCC__
 void pgo_sparse_launch(const PgoSparseDev& d, const PgoSparsePlan& pl, hipStream_t s);      // one trial's solve
+// its first two stages on their own (plba_pose_graph_marginals factors and then inverts): k_sps_assemble over every front, and
+// k_sps_factor over the fronts lv[l0 .. l0 + count) of one level
+void pgo_sparse_launch_assemble(const PgoSparseDev& d, const PgoSparsePlan& pl, hipStream_t s);
+void pgo_sparse_launch_factor(const PgoSparseDev& d, int l0, int count, hipStream_t s);
 #endif
 
 // blk_row / blk_col: the free ranks of every block of H (row >= column); diagonal blocks exist for every free rank.

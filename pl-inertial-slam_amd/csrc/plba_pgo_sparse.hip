@@ -210,10 +210,17 @@ __global__ __launch_bounds__(SPT) void k_sps_back(PgoSparseDev d, int l0) {
 
 }  // namespace
 
-void pgo_sparse_launch(const PgoSparseDev& d, const PgoSparsePlan& pl, hipStream_t s) {
+void pgo_sparse_launch_assemble(const PgoSparseDev& d, const PgoSparsePlan& pl, hipStream_t s) {
     hipLaunchKernelGGL(k_sps_assemble, dim3((unsigned)pl.nfront), dim3(SPT), 0, s, d);
-    for (int l = 0; l < pl.nlev; ++l)
-        hipLaunchKernelGGL(k_sps_factor, dim3((unsigned)(pl.lv_start[l + 1] - pl.lv_start[l])), dim3(SPT), 0, s, d, pl.lv_start[l]);
+}
+
+void pgo_sparse_launch_factor(const PgoSparseDev& d, int l0, int count, hipStream_t s) {
+    hipLaunchKernelGGL(k_sps_factor, dim3((unsigned)count), dim3(SPT), 0, s, d, l0);
+}
+
+void pgo_sparse_launch(const PgoSparseDev& d, const PgoSparsePlan& pl, hipStream_t s) {
+    pgo_sparse_launch_assemble(d, pl, s);
+    for (int l = 0; l < pl.nlev; ++l) pgo_sparse_launch_factor(d, pl.lv_start[l], pl.lv_start[l + 1] - pl.lv_start[l], s);
     for (int l = pl.nlev - 1; l >= 0; --l)
         hipLaunchKernelGGL(k_sps_back, dim3((unsigned)(pl.lv_start[l + 1] - pl.lv_start[l])), dim3(SPT), 0, s, d, pl.lv_start[l]);
 }

@@ -318,6 +318,8 @@ struct plba_problem {
     plba::MargPending* mp = nullptr;      // the marginalization that makes it, while it may still be in the stream (resolved by its first consumer)
     double pgo_sparse[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // last plba_optimize_pose_graph (plba_debug_get "pgo_sparse", include/plba.h)
     double lba_sparse[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // last plba_lba_visual (plba_debug_get "lba_sparse", include/plba.h)
+    double pgo_cov[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // last plba_pose_graph_marginals (plba_debug_get "pgo_cov", include/plba.h)
+    std::vector<double> pgo_cov_H;                     // options.diag & PLBA_DIAG_PGO_COV_DUMP: the device's Hblk (nblk x 36) of that call (plba_debug_get "pgo_cov_H")
     plba::BowState* bow = nullptr;       // place recognition (plba_bow_*): made by the first plba_bow_set_vocabulary, dropped by plba_bow_discard()
     long host_waits = 0;                  // times the library blocked the calling thread on the device (plba_debug_get "host_waits")
     plba::Robust rob;
