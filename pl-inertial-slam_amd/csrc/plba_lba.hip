@@ -19,10 +19,10 @@
 // plba_lba_options.solver = 1 (the whole-map runs) keeps the reduced camera system as the list of its nonzero 6 x 6 blocks
 // (plba_lba_sparse.h) and replaces  memset + k_lba_sysinit + k_lba_pairs + Cholesky / back-substitution  by  k_lba_sblk (a wave per
 // block: its pair entries summed in a fixed order, no atomics) -> k_lba_rhs into a P-vector -> the multifrontal solve of
-// plba_pgo_sparse.h -> k_lba_smerge; everything else of a pass, and the control, is the same code.
+// plba_pgo_sparse.h (on the device through a PgoSparseWork) -> k_lba_smerge; everything else of a pass, and the control, is the same code.
 #include "plba_internal.h"
 #include "plba_lba_sparse.h"
-#include "plba_pgo_sparse.h"
+#include "plba_pgo_sparse_dev.h"
 #include "plba_problem.h"
 #include <chrono>
 #include <cstddef>
@@ -781,37 +781,23 @@ int plba_lba_visual(plba_problem* p, const plba_lba_options* opt, int K, const d
     std::vector<int32_t> pair_ent, chunk;
     LbaBlockList blist;          // the sparse solver's: the same entries grouped by block of S, nothing of size Nkf x Nkf
     PgoSparsePlan plan;
-    double srec[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // plba_debug_get "lba_sparse", kept when the call has succeeded
+    double srec[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ms_analysis = 0.0;      // plba_debug_get "lba_sparse", kept when the call has succeeded
     if (sparse) {
         if (!lba_block_list(Nkf, L, lm_start.data(), obs_kf.data(), kf_loc, blist)) FAIL(p, PLBA_ERR_INVALID, "plba_lba_visual: too many co-observation pairs");
         const auto ta = std::chrono::steady_clock::now();
         if (!pgo_sparse_analyse(Nkf, blist.blk_row, blist.blk_col, plan)) FAIL(p, PLBA_ERR_INTERNAL, "plba_lba_visual: the sparse analysis failed its checks");
-        srec[7] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ta).count();
-        srec[0] = 1.0; srec[1] = Nkf; srec[2] = plan.nfront; srec[3] = plan.nlev; srec[4] = (double)plan.nnz_blk; srec[5] = plan.max_m;
+        ms_analysis = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ta).count();
         pair_ent.swap(blist.pair_ent);
         if (pair_ent.empty()) pair_ent.assign(2, 0);
-        if (plan.ch.empty()) plan.ch.assign(1, 0);
     } else {
         std::vector<int64_t> cnt((size_t)Nkf * Nkf + 1, 0);
-        auto for_pairs = [&](auto&& fn) {
-            for (int l = 0; l < L; ++l)
-                for (int ea = lm_start[l]; ea < lm_start[l + 1]; ++ea) {
-                    const int la = kf_loc[obs_kf[ea]];
-                    if (la < 0) continue;
-                    for (int eb = lm_start[l]; eb < lm_start[l + 1]; ++eb) {
-                        const int lb = kf_loc[obs_kf[eb]];
-                        if (lb < la) continue;      // the (lb, la) block is the transpose; la == lb keeps every ordered pair (normally just the observation with itself)
-                        fn(la, lb, ea, eb);
-                    }
-                }
-        };
-        for_pairs([&](int la, int lb, int, int) { ++cnt[(size_t)la * Nkf + lb + 1]; });
+        lba_for_pairs(L, lm_start.data(), obs_kf.data(), kf_loc, [&](int la, int lb, int, int) { ++cnt[(size_t)la * Nkf + lb + 1]; });
         for (size_t i = 0; i < (size_t)Nkf * Nkf; ++i) cnt[i + 1] += cnt[i];
         const int64_t nent = cnt[(size_t)Nkf * Nkf];
         if (nent > INT32_MAX / 2) FAIL(p, PLBA_ERR_INVALID, "plba_lba_visual: too many co-observation pairs");
         pair_ent.assign((size_t)2 * std::max<int64_t>(nent, 1), 0);
         std::vector<int64_t> cur(cnt.begin(), cnt.end() - 1);
-        for_pairs([&](int la, int lb, int ea, int eb) { const int64_t t = cur[(size_t)la * Nkf + lb]++; pair_ent[2 * t] = ea; pair_ent[2 * t + 1] = eb; });
+        lba_for_pairs(L, lm_start.data(), obs_kf.data(), kf_loc, [&](int la, int lb, int ea, int eb) { const int64_t t = cur[(size_t)la * Nkf + lb]++; pair_ent[2 * t] = ea; pair_ent[2 * t + 1] = eb; });
         for (int la = 0; la < Nkf; ++la)
             for (int lb = la; lb < Nkf; ++lb)
                 for (int64_t t0 = cnt[(size_t)la * Nkf + lb], t1 = cnt[(size_t)la * Nkf + lb + 1]; t0 < t1; t0 += PAIR_CHUNK) {
@@ -830,9 +816,8 @@ int plba_lba_visual(plba_problem* p, const plba_lba_options* opt, int K, const d
     DArr<int32_t> dloc, dlockf, dlms, dokf, dkfs, dkfo, dpent, dchunk;
     DArr<double> dUrec;
     DenseWork work; DArr<Ctrl> ctrl, lmctrl;
-    DArr<int32_t> sb_start, sb_row, sb_col, sp_m, sp_np, sp_row0, sp_rows, sp_umap, sp_chs, sp_ch, sp_ass, sp_as, sp_lv;      // the sparse solver's
-    DArr<long long> sp_off, sp_roff;
-    DArr<double> sp_F, sp_R, dHblk, db, xx;
+    DArr<int32_t> sb_start, sb_row, sb_col;      // the sparse solver's
+    DArr<double> dHblk, db, xx; PgoSparseWork swork;
     Ctrl lm0; memset(&lm0, 0, sizeof lm0); lm0.solver_ok = 1;
     const std::vector<Ctrl> hlm0(1, lm0);
     const int nsblk = (int)blist.blk_row.size();
@@ -850,11 +835,7 @@ int plba_lba_visual(plba_problem* p, const plba_lba_options* opt, int K, const d
         HIPCK(p, ctrl.alloc(1)); HIPCK(p, dTout.alloc((size_t)16 * K));
         if (sparse) {      // the block list, the plan, the fronts; no sys, no DenseWork, no dense x
             HIPCK(p, sb_start.upload(blist.blk_start)); HIPCK(p, sb_row.upload(blist.blk_row)); HIPCK(p, sb_col.upload(blist.blk_col));
-            HIPCK(p, dHblk.alloc((size_t)36 * nsblk)); HIPCK(p, db.alloc(P)); HIPCK(p, xx.alloc(P)); HIPCK(p, lmctrl.upload(hlm0));
-            HIPCK(p, sp_m.upload(plan.f_m)); HIPCK(p, sp_np.upload(plan.f_np)); HIPCK(p, sp_row0.upload(plan.f_row0)); HIPCK(p, sp_rows.upload(plan.rows));
-            HIPCK(p, sp_umap.upload(plan.umap)); HIPCK(p, sp_chs.upload(plan.ch_start)); HIPCK(p, sp_ch.upload(plan.ch)); HIPCK(p, sp_ass.upload(plan.as_start));
-            HIPCK(p, sp_as.upload(plan.as)); HIPCK(p, sp_lv.upload(plan.lv)); HIPCK(p, sp_off.upload(plan.f_off)); HIPCK(p, sp_roff.upload(plan.f_roff));
-            HIPCK(p, sp_F.alloc((size_t)plan.fsize, false)); HIPCK(p, sp_R.alloc((size_t)plan.rsize, false));
+            HIPCK(p, dHblk.alloc((size_t)36 * nsblk)); HIPCK(p, db.alloc(P)); HIPCK(p, xx.alloc(P)); HIPCK(p, lmctrl.upload(hlm0)); HIPCK(p, swork.upload(plan));
         } else {
             HIPCK(p, dchunk.upload(chunk)); HIPCK(p, sys.alloc(sysn)); HIPCK(p, work.alloc(Ppad, ld, ninv_fits(Ppad)));
         }
@@ -871,14 +852,11 @@ int plba_lba_visual(plba_problem* p, const plba_lba_options* opt, int K, const d
     PgoSparseDev sd; memset(&sd, 0, sizeof sd);
     if (sparse) {
         d.x = xx.p; d.rhs = db.p; d.sb_start = sb_start.p; d.sb_row = sb_row.p; d.sb_col = sb_col.p; d.Hblk = dHblk.p; d.lmctrl = lmctrl.p;
-        sd.f_m = sp_m.p; sd.f_np = sp_np.p; sd.f_row0 = sp_row0.p; sd.rows = sp_rows.p; sd.umap = sp_umap.p; sd.ch_start = sp_chs.p; sd.ch = sp_ch.p;
-        sd.as_start = sp_ass.p; sd.as = sp_as.p; sd.lv = sp_lv.p; sd.f_off = sp_off.p; sd.f_roff = sp_roff.p; sd.F = sp_F.p; sd.R = sp_R.p;
-        sd.Hblk = dHblk.p; sd.b = db.p; sd.x = xx.p; sd.c = ctrl.p /* lambda = 0: the blocks are damped already */;
-        size_t bytes = 0;
+        swork.bind(sd); sd.Hblk = dHblk.p; sd.b = db.p; sd.x = xx.p; sd.c = ctrl.p /* lambda = 0: the blocks are damped already */;
+        size_t bytes = swork.bytes();
         auto add = [&](const auto& a) { bytes += a.n * sizeof(*a.p); };
-        add(dpent); add(sb_start); add(sb_row); add(sb_col); add(dHblk); add(db); add(xx); add(lmctrl); add(sp_m); add(sp_np); add(sp_row0); add(sp_rows);
-        add(sp_umap); add(sp_chs); add(sp_ch); add(sp_ass); add(sp_as); add(sp_lv); add(sp_off); add(sp_roff); add(sp_F); add(sp_R);
-        srec[6] = (double)bytes;
+        add(dpent); add(sb_start); add(sb_row); add(sb_col); add(dHblk); add(db); add(xx); add(lmctrl);
+        pgo_sparse_record(srec, Nkf, plan, bytes, ms_analysis);
     } else {
         d.rhs = sys.p + (size_t)Ppad * ld;
         dd.P = P; dd.Ppad = Ppad; dd.ld = ld; dd.sys = sys.p; dd.ctrl = ctrl.p; work.bind(dd, p->opt);

@@ -4,9 +4,9 @@
 //
 // S has one 6 x 6 block per local keyframe on its diagonal and one block (lb, la), lb > la, per pair of local keyframes that observe a
 // common landmark (the covisibility graph).  A Schur pair entry is a pair of observations (ea, eb) of ONE landmark from the local
-// keyframes la <= lb (an observation with itself included; la == lb keeps every ordered pair), exactly what the dense path's for_pairs
-// enumerates: landmark by landmark, ea ascending, eb ascending.  Here the entries are sorted by block with two stable counting passes
-// (by lb, then by la), so that
+// keyframes la <= lb (an observation with itself included; la == lb keeps every ordered pair), exactly what lba_for_pairs below
+// enumerates for both solvers: landmark by landmark, ea ascending, eb ascending.  Here the entries are sorted by block with two stable
+// counting passes (by lb, then by la), so that
 //   blocks    come in ascending (la, lb): every keyframe's diagonal block first (it exists even without an entry: a keyframe that
 //             observes nothing keeps its zero block, and the factorisation reports the zero pivot), then its blocks with lb > la;
 //   entries   of one block keep the enumeration order above, the order in which the dense path's pair list holds them.
@@ -27,31 +27,34 @@ struct LbaBlockList {
 
 constexpr int64_t LBA_MAX_PAIR_ENT = INT32_MAX / 2;
 
+// The Schur pair entries in enumeration order, fn(la, lb, ea, eb) for each: the one definition both solvers' lists are built from.
 // lm_start (L + 1) / obs_kf: the landmark-major observation lists; kf_loc[k] = local index of keyframe k or < 0.
+template <class Fn>
+inline void lba_for_pairs(int L, const int32_t* lm_start, const int32_t* obs_kf, const int32_t* kf_loc, Fn&& fn) {
+    for (int l = 0; l < L; ++l)
+        for (int ea = lm_start[l]; ea < lm_start[l + 1]; ++ea) {
+            const int la = kf_loc[obs_kf[ea]];
+            if (la < 0) continue;
+            for (int eb = lm_start[l]; eb < lm_start[l + 1]; ++eb) {
+                const int lb = kf_loc[obs_kf[eb]];
+                if (lb < la) continue;      // the (lb, la) block is the transpose; la == lb keeps every ordered pair (normally just the observation with itself)
+                fn(la, lb, ea, eb);
+            }
+        }
+}
+
 // false: more than LBA_MAX_PAIR_ENT entries (nothing is built)
 inline bool lba_block_list(int Nkf, int L, const int32_t* lm_start, const int32_t* obs_kf, const int32_t* kf_loc, LbaBlockList& out) {
     out = LbaBlockList();
-    auto for_pairs = [&](auto&& fn) {
-        for (int l = 0; l < L; ++l)
-            for (int ea = lm_start[l]; ea < lm_start[l + 1]; ++ea) {
-                const int la = kf_loc[obs_kf[ea]];
-                if (la < 0) continue;
-                for (int eb = lm_start[l]; eb < lm_start[l + 1]; ++eb) {
-                    const int lb = kf_loc[obs_kf[eb]];
-                    if (lb < la) continue;
-                    fn(la, lb, ea, eb);
-                }
-            }
-    };
     // pass 1: count by lb, place in enumeration order
     std::vector<int64_t> cb((size_t)Nkf + 1, 0), ca((size_t)Nkf + 1, 0);
     int64_t nent = 0;
-    for_pairs([&](int la, int lb, int, int) { ++cb[lb + 1]; ++ca[la + 1]; ++nent; });
+    lba_for_pairs(L, lm_start, obs_kf, kf_loc, [&](int la, int lb, int, int) { ++cb[lb + 1]; ++ca[la + 1]; ++nent; });
     if (nent > LBA_MAX_PAIR_ENT) return false;
     for (int i = 0; i < Nkf; ++i) { cb[i + 1] += cb[i]; ca[i + 1] += ca[i]; }
     struct Ent { int32_t la, lb, ea, eb; };
     std::vector<Ent> by_b((size_t)nent);
-    for_pairs([&](int la, int lb, int ea, int eb) { by_b[(size_t)cb[lb]++] = Ent{la, lb, ea, eb}; });
+    lba_for_pairs(L, lm_start, obs_kf, kf_loc, [&](int la, int lb, int ea, int eb) { by_b[(size_t)cb[lb]++] = Ent{la, lb, ea, eb}; });
     // pass 2: stable by la: ascending (la, lb), enumeration order within a block
     std::vector<Ent> s((size_t)nent);
     for (const Ent& e : by_b) s[(size_t)ca[e.la]++] = e;

@@ -1,7 +1,8 @@
 // plba_lba_sparse_hostcheck.cpp — a stand-alone program over plba_lba_sparse.h, the block list of the reduced camera matrix that
 // plba_lba_visual builds for its sparse solve (plba_lba_options.solver = 1).  Built with a plain C++ compiler under the address and
 // undefined-behaviour sanitizers and run directly by tests/test_lba_sparse_cpu.py.  Every list is compared, element by element, with a
-// brute-force enumeration: for every keyframe pair la <= lb in ascending order, every landmark, every ordered pair of its observations.
+// brute-force enumeration: for every keyframe pair la <= lb in ascending order, every landmark, every ordered pair of its observations;
+// lba_for_pairs, which both solvers' lists are built from, is run on its own as well.
 // Prints one line per window, `ok <window>`, and exits 0; the first failed check prints its text and exits 1.
 #include <cstdio>
 #include <cstdlib>
@@ -45,6 +46,15 @@ static void check(const char* name, const Win& w) {
     CHECK(bl.blk_col == col);
     CHECK(bl.blk_start == start);
     CHECK(bl.pair_ent == ent);
+    // the shared enumerator on its own, as the dense solver's list takes it: the same entries, ea ascending and eb ascending within it
+    int64_t seen = 0;
+    int pea = -1, peb = -1;
+    lba_for_pairs(L, lm_start.data(), obs_kf.data(), kf_loc.data(), [&](int la, int lb, int ea, int eb) {
+        CHECK(la >= 0 && la <= lb && kf_loc[obs_kf[ea]] == la && kf_loc[obs_kf[eb]] == lb);
+        CHECK(ea > pea || (ea == pea && eb > peb));
+        pea = ea; peb = eb; ++seen;
+    });
+    CHECK(seen == bl.nent);
     // what the analysis and the kernels rely on: a diagonal block per keyframe, row >= column, no block twice, entries of the block's keyframes
     std::vector<int> diag(Nkf, 0);
     for (size_t k = 0; k < bl.blk_row.size(); ++k) {

@@ -22,7 +22,7 @@
 //   k_pgo_edges<errors>   the trial's chi2 per edge
 //   k_pgo_decide          tempChi, scale, rho, the g2o lambda schedule, restore on rejection, trace row, loop exits, mailbox
 // options.pgo_solver = 1 replaces k_pgo_fill + launch_cholesky + launch_trsv_back by the multifrontal solve of plba_pgo_sparse.h
-// (no blkmap and no dense image; the structure is analysed once per call on the host).
+// (no blkmap and no dense image; the structure is analysed once per call on the host and held on the device by a PgoSparseWork).
 // Every kernel but the factorisation returns at once after the run has ended (PgoCtl::done).  Nothing of O(P^2) or O(E)
 // crosses PCIe between the upload and the read-back of the poses, the control block and the trace.
 // Bit-reproducible: no floating-point atomics; every sum has one owner and a fixed order.
@@ -35,7 +35,7 @@
 
 #include "plba_internal.h"
 #include "plba_pgo_cov.h"
-#include "plba_pgo_sparse.h"
+#include "plba_pgo_sparse_dev.h"
 #include "plba_problem.h"
 
 #define HIPCK(p, call) PLBA_HIPCK(p, call)
@@ -466,6 +466,21 @@ int pgo_graph_setup(plba_problem* p, const plba_pose_graph* g, const char* who, 
     return PLBA_OK;
 }
 
+// What k_pgo_edges reads of the edges of a graph that has passed pgo_graph_setup: the inverse measurements, the information matrices
+// (the identity where the graph gives none) and the endpoints.  Without an edge all four stay empty (DArr::upload: one zeroed element).
+struct PgoEdges { std::vector<double> Zi, info; std::vector<int32_t> ei, ej; };
+PgoEdges pgo_stage_edges(const plba_pose_graph* g) {
+    const int ne = g->ne; PgoEdges e;
+    e.Zi.assign((size_t)12 * ne, 0.0); e.info.assign((size_t)36 * ne, 0.0);
+    for (int k = 0; k < ne; ++k) {
+        h_store(h_inv(h_load(g->meas12 + (size_t)12 * k)), &e.Zi[(size_t)12 * k]);
+        if (g->info36) memcpy(&e.info[(size_t)36 * k], g->info36 + (size_t)36 * k, 36 * 8);
+        else for (int i = 0; i < 6; ++i) e.info[(size_t)36 * k + 7 * i] = 1.0;
+    }
+    if (ne > 0) { e.ei.assign(g->ei, g->ei + ne); e.ej.assign(g->ej, g->ej + ne); }
+    return e;
+}
+
 }  // namespace
 }  // namespace plba
 
@@ -519,14 +534,13 @@ int plba_optimize_pose_graph(plba_problem* p, plba_pose_graph* g, int max_iters,
     const bool run = max_iters > 0 && n > 0, sparse = p->opt.pgo_solver == 1;
     std::vector<int32_t>&blk_start = gs.blk_start, &blk_src = gs.blk_src, &blk_diag = gs.blk_diag, &blk_row = gs.blk_row, &blk_col = gs.blk_col, &dg_blk = gs.dg_blk, &blkmap = gs.blkmap;
     const int nblk = (int)blk_row.size();
-    PgoSparsePlan plan;
+    PgoSparsePlan plan; double ms_analysis = 0.0;
     if (sparse) {
         p->pgo_sparse[0] = 1.0;
         if (run) {
             const auto ta = std::chrono::steady_clock::now();
             if (!pgo_sparse_analyse(n, blk_row, blk_col, plan)) FAIL(p, PLBA_ERR_INVALID, "plba_optimize_pose_graph: the sparse analysis failed its checks");
-            p->pgo_sparse[1] = n; p->pgo_sparse[2] = plan.nfront; p->pgo_sparse[3] = plan.nlev; p->pgo_sparse[4] = (double)plan.nnz_blk; p->pgo_sparse[5] = plan.max_m;
-            p->pgo_sparse[7] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ta).count();
+            ms_analysis = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ta).count();
         }
     }
 
@@ -535,23 +549,10 @@ int plba_optimize_pose_graph(plba_problem* p, plba_pose_graph* g, int max_iters,
     hipStream_t s = p->stream;
     const int Ppad = dense_ppad(P), ld = Ppad;
     const size_t sysn = run && !sparse ? (size_t)(Ppad + TILE) * ld : 1;
-    std::vector<double> Zi((size_t)12 * std::max(ne, 1), 0.0), info((size_t)36 * std::max(ne, 1), 0.0);
-    for (int k = 0; k < ne; ++k) {
-        h_store(h_inv(h_load(g->meas12 + (size_t)12 * k)), &Zi[(size_t)12 * k]);
-        if (g->info36) memcpy(&info[(size_t)36 * k], g->info36 + (size_t)36 * k, 36 * 8);
-        else for (int i = 0; i < 6; ++i) info[(size_t)36 * k + 7 * i] = 1.0;
-    }
-    std::vector<int32_t> hei(g->ei ? g->ei : nullptr, g->ei ? g->ei + ne : nullptr), hej(g->ej ? g->ej : nullptr, g->ej ? g->ej + ne : nullptr);
-    if (hei.empty()) { hei.assign(1, 0); hej.assign(1, 0); }
-    if (free_v.empty()) free_v.assign(1, 0);
-    auto nz = [](std::vector<int32_t>& v) { if (v.empty()) v.assign(1, 0); };
-    nz(blk_start); nz(blk_src); nz(blk_diag); nz(blk_row); nz(dg_blk); nz(blkmap);
+    const PgoEdges he = pgo_stage_edges(g);
     DArr<double> dX, dXs, dZi, dInfo, dErec, dEchi, dHblk, db, sys, xx /* the sparse solve's */;
     DArr<int32_t> dfree, dei, dej, dbs, dbsrc, dbdiag, dbrow, ddg, dmap;
-    DArr<int> dcnt; DenseWork work;
-    DArr<int32_t> sp_m, sp_np, sp_row0, sp_rows, sp_umap, sp_chs, sp_ch, sp_ass, sp_as, sp_lv;
-    DArr<long long> sp_off, sp_roff;
-    DArr<double> sp_F, sp_R;
+    DArr<int> dcnt; DenseWork work; PgoSparseWork swork;
     DArr<PgoCtl> dctl;
     DArr<plba_trace_row> dtrace;
     PgoCtl c0; memset(&c0, 0, sizeof c0);
@@ -560,7 +561,7 @@ int plba_optimize_pose_graph(plba_problem* p, plba_pose_graph* g, int max_iters,
     {
         DArrStreamScope staged(s, p->have_ctx ? p->ctx.stage : nullptr);      // host vectors above stay alive until the wait below
         HIPCK(p, dX.upload(X)); HIPCK(p, dXs.alloc((size_t)12 * nv)); HIPCK(p, dcnt.alloc(nv));
-        HIPCK(p, dZi.upload(Zi)); HIPCK(p, dInfo.upload(info)); HIPCK(p, dei.upload(hei)); HIPCK(p, dej.upload(hej));
+        HIPCK(p, dZi.upload(he.Zi)); HIPCK(p, dInfo.upload(he.info)); HIPCK(p, dei.upload(he.ei)); HIPCK(p, dej.upload(he.ej));
         HIPCK(p, dEchi.alloc(std::max(ne, 1))); HIPCK(p, dctl.upload(hc0)); HIPCK(p, dtrace.alloc(std::max(trace_cap, 1)));
         if (run) {
             HIPCK(p, dfree.upload(free_v)); HIPCK(p, dbs.upload(blk_start)); HIPCK(p, dbsrc.upload(blk_src));
@@ -568,12 +569,7 @@ int plba_optimize_pose_graph(plba_problem* p, plba_pose_graph* g, int max_iters,
             if (!sparse) HIPCK(p, dmap.upload(blkmap));
             HIPCK(p, dErec.alloc((size_t)PGO_REC * std::max(ne, 1))); HIPCK(p, dHblk.alloc((size_t)36 * std::max(nblk, 1))); HIPCK(p, db.alloc(P));
             if (sparse) {
-                HIPCK(p, xx.alloc(P));
-                HIPCK(p, sp_m.upload(plan.f_m)); HIPCK(p, sp_np.upload(plan.f_np)); HIPCK(p, sp_row0.upload(plan.f_row0)); HIPCK(p, sp_rows.upload(plan.rows));
-                HIPCK(p, sp_umap.upload(plan.umap)); HIPCK(p, sp_chs.upload(plan.ch_start)); HIPCK(p, sp_ass.upload(plan.as_start)); HIPCK(p, sp_as.upload(plan.as));
-                HIPCK(p, sp_lv.upload(plan.lv)); HIPCK(p, sp_off.upload(plan.f_off)); HIPCK(p, sp_roff.upload(plan.f_roff));
-                if (plan.ch.empty()) plan.ch.assign(1, 0);
-                HIPCK(p, sp_ch.upload(plan.ch)); HIPCK(p, sp_F.alloc((size_t)plan.fsize, false)); HIPCK(p, sp_R.alloc((size_t)plan.rsize, false));
+                HIPCK(p, xx.alloc(P)); HIPCK(p, swork.upload(plan));
             } else {
                 HIPCK(p, sys.alloc(sysn, false)); HIPCK(p, work.alloc(Ppad, ld, ninv_fits(Ppad)));
             }
@@ -588,15 +584,12 @@ int plba_optimize_pose_graph(plba_problem* p, plba_pose_graph* g, int max_iters,
     d.Hblk = dHblk.p; d.b = db.p; d.sys = sys.p; d.x = sparse ? xx.p : work.x.p; d.ctl = dctl.p; d.mail = reinterpret_cast<PgoMail*>(p->d_mail); d.trace = dtrace.p;
     PgoSparseDev sd; memset(&sd, 0, sizeof sd);
     if (sparse && run) {
-        sd.f_m = sp_m.p; sd.f_np = sp_np.p; sd.f_row0 = sp_row0.p; sd.rows = sp_rows.p; sd.umap = sp_umap.p; sd.ch_start = sp_chs.p; sd.ch = sp_ch.p;
-        sd.as_start = sp_ass.p; sd.as = sp_as.p; sd.lv = sp_lv.p; sd.f_off = sp_off.p; sd.f_roff = sp_roff.p; sd.F = sp_F.p; sd.R = sp_R.p;
-        sd.Hblk = dHblk.p; sd.b = db.p; sd.x = xx.p; sd.c = &dctl.p->c; sd.done = &dctl.p->done;
-        size_t bytes = 0;
+        swork.bind(sd); sd.Hblk = dHblk.p; sd.b = db.p; sd.x = xx.p; sd.c = &dctl.p->c; sd.done = &dctl.p->done;
+        size_t bytes = swork.bytes();
         auto add = [&](const auto& a) { bytes += a.n * sizeof(*a.p); };
         add(dX); add(dXs); add(dcnt); add(dZi); add(dInfo); add(dei); add(dej); add(dEchi); add(dctl); add(dtrace); add(dfree); add(dbs); add(dbsrc);
-        add(dbdiag); add(dbrow); add(ddg); add(dErec); add(dHblk); add(db); add(xx); add(sp_m); add(sp_np); add(sp_row0); add(sp_rows); add(sp_umap);
-        add(sp_chs); add(sp_ch); add(sp_ass); add(sp_as); add(sp_lv); add(sp_off); add(sp_roff); add(sp_F); add(sp_R);
-        p->pgo_sparse[6] = (double)bytes;
+        add(dbdiag); add(dbrow); add(ddg); add(dErec); add(dHblk); add(db); add(xx);
+        pgo_sparse_record(p->pgo_sparse, n, plan, bytes, ms_analysis);
     }
     DevBuf dd; memset(&dd, 0, sizeof dd);
     dd.P = P; dd.Ppad = Ppad; dd.ld = ld; dd.sys = sys.p; dd.ctrl = &dctl.p->c; work.bind(dd, p->opt);
@@ -704,22 +697,12 @@ int plba_pose_graph_marginals(plba_problem* p, const plba_pose_graph* g, plba_pg
     HIPCK(p, hipSetDevice(p->device));
     hipStream_t s = p->stream;
     std::vector<double> X(g->pose12, g->pose12 + (size_t)12 * nv);
-    std::vector<double> Zi((size_t)12 * std::max(ne, 1), 0.0), info((size_t)36 * std::max(ne, 1), 0.0);
-    for (int k = 0; k < ne; ++k) {
-        h_store(h_inv(h_load(g->meas12 + (size_t)12 * k)), &Zi[(size_t)12 * k]);
-        if (g->info36) memcpy(&info[(size_t)36 * k], g->info36 + (size_t)36 * k, 36 * 8);
-        else for (int i = 0; i < 6; ++i) info[(size_t)36 * k + 7 * i] = 1.0;
-    }
-    std::vector<int32_t> hei(g->ei ? g->ei : nullptr, g->ei ? g->ei + ne : nullptr), hej(g->ej ? g->ej : nullptr, g->ej ? g->ej + ne : nullptr);
-    if (hei.empty()) { hei.assign(1, 0); hej.assign(1, 0); }
-    auto nz = [](std::vector<int32_t>& v) { if (v.empty()) v.assign(1, 0); };
-    nz(gs.blk_start); nz(gs.blk_src); nz(gs.blk_diag); nz(gs.blk_row);
+    const PgoEdges he = pgo_stage_edges(g);      // (these and the block lists go up only with a free vertex, and then none of them is empty)
     std::vector<int32_t> hplace((size_t)4 * places.size());
     for (size_t i = 0; i < places.size(); ++i) { hplace[4 * i] = places[i].front; hplace[4 * i + 1] = places[i].rpos; hplace[4 * i + 2] = places[i].cpos; hplace[4 * i + 3] = places[i].transposed; }
-    DArr<double> dX, dZi, dInfo, dErec, dEchi, dHblk, db, sp_F, sp_R, dG, dOut;
+    DArr<double> dX, dZi, dInfo, dErec, dEchi, dHblk, db, dG, dOut;
     DArr<int32_t> dei, dej, dbs, dbsrc, dbdiag, dbrow, dplace, dpar;
-    DArr<int32_t> sp_m, sp_np, sp_row0, sp_rows, sp_umap, sp_chs, sp_ch, sp_ass, sp_as, sp_lv;
-    DArr<long long> sp_off, sp_roff, dgoff;
+    DArr<long long> dgoff; PgoSparseWork swork;
     DArr<uint8_t> dstatus;
     DArr<PgoCtl> dctl;
     DArr<int> drec;
@@ -735,16 +718,11 @@ int plba_pose_graph_marginals(plba_problem* p, const plba_pose_graph* g, plba_pg
         HIPCK(p, dctl.upload(hc0)); HIPCK(p, drec.upload(hrec)); HIPCK(p, dplace.upload(hplace)); HIPCK(p, dstatus.upload(status));
         HIPCK(p, dOut.alloc(HEAD + (size_t)36 * std::max(n_items, 1), false));
         if (n > 0) {
-            HIPCK(p, dX.upload(X)); HIPCK(p, dZi.upload(Zi)); HIPCK(p, dInfo.upload(info)); HIPCK(p, dei.upload(hei)); HIPCK(p, dej.upload(hej));
+            HIPCK(p, dX.upload(X)); HIPCK(p, dZi.upload(he.Zi)); HIPCK(p, dInfo.upload(he.info)); HIPCK(p, dei.upload(he.ei)); HIPCK(p, dej.upload(he.ej));
             HIPCK(p, dEchi.alloc(std::max(ne, 1))); HIPCK(p, dErec.alloc((size_t)PGO_REC * std::max(ne, 1)));
             HIPCK(p, dbs.upload(gs.blk_start)); HIPCK(p, dbsrc.upload(gs.blk_src)); HIPCK(p, dbdiag.upload(gs.blk_diag)); HIPCK(p, dbrow.upload(gs.blk_row));
             HIPCK(p, dHblk.alloc((size_t)36 * std::max(nblk, 1))); HIPCK(p, db.alloc(P));
-            HIPCK(p, sp_m.upload(plan.f_m)); HIPCK(p, sp_np.upload(plan.f_np)); HIPCK(p, sp_row0.upload(plan.f_row0)); HIPCK(p, sp_rows.upload(plan.rows));
-            HIPCK(p, sp_umap.upload(plan.umap)); HIPCK(p, sp_chs.upload(plan.ch_start)); HIPCK(p, sp_ass.upload(plan.as_start)); HIPCK(p, sp_as.upload(plan.as));
-            HIPCK(p, sp_lv.upload(plan.lv)); HIPCK(p, sp_off.upload(plan.f_off)); HIPCK(p, sp_roff.upload(plan.f_roff));
-            if (plan.ch.empty()) plan.ch.assign(1, 0);
-            HIPCK(p, sp_ch.upload(plan.ch)); HIPCK(p, sp_F.alloc((size_t)plan.fsize, false)); HIPCK(p, sp_R.alloc((size_t)plan.rsize, false));
-            HIPCK(p, dpar.upload(cp.parent)); HIPCK(p, dgoff.upload(cp.g_off)); HIPCK(p, dG.alloc((size_t)cp.gsize, false));
+            HIPCK(p, swork.upload(plan)); HIPCK(p, dpar.upload(cp.parent)); HIPCK(p, dgoff.upload(cp.g_off)); HIPCK(p, dG.alloc((size_t)cp.gsize, false));
         }
     }
     PgoDev d; memset(&d, 0, sizeof d);
@@ -752,23 +730,20 @@ int plba_pose_graph_marginals(plba_problem* p, const plba_pose_graph* g, plba_pg
     d.X = dX.p; d.ei = dei.p; d.ej = dej.p; d.Zi = dZi.p; d.info = dInfo.p; d.erec = dErec.p; d.echi = dEchi.p;
     d.blk_start = dbs.p; d.blk_src = dbsrc.p; d.blk_diag = dbdiag.p; d.blk_row = dbrow.p; d.Hblk = dHblk.p; d.b = db.p; d.ctl = dctl.p;
     PgoSparseDev sd; memset(&sd, 0, sizeof sd);
-    sd.f_m = sp_m.p; sd.f_np = sp_np.p; sd.f_row0 = sp_row0.p; sd.rows = sp_rows.p; sd.umap = sp_umap.p; sd.ch_start = sp_chs.p; sd.ch = sp_ch.p;
-    sd.as_start = sp_ass.p; sd.as = sp_as.p; sd.lv = sp_lv.p; sd.f_off = sp_off.p; sd.f_roff = sp_roff.p; sd.F = sp_F.p; sd.R = sp_R.p;
-    sd.Hblk = dHblk.p; sd.b = db.p; sd.c = &dctl.p->c; sd.done = &dctl.p->done;
+    swork.bind(sd); sd.Hblk = dHblk.p; sd.b = db.p; sd.c = &dctl.p->c; sd.done = &dctl.p->done;
     PgoCovDev cd; memset(&cd, 0, sizeof cd);
     cd.parent = dpar.p; cd.g_off = dgoff.p; cd.G = dG.p; cd.n_items = n_items; cd.place = dplace.p; cd.status = dstatus.p; cd.out = dOut.p + HEAD;
-    size_t bytes = 0;
+    size_t bytes = swork.bytes();
     {
         auto add = [&](const auto& a) { bytes += a.n * sizeof(*a.p); };
-        add(dX); add(dZi); add(dInfo); add(dErec); add(dEchi); add(dHblk); add(db); add(sp_F); add(sp_R); add(dG); add(dOut); add(dei); add(dej); add(dbs);
-        add(dbsrc); add(dbdiag); add(dbrow); add(dplace); add(dpar); add(sp_m); add(sp_np); add(sp_row0); add(sp_rows); add(sp_umap); add(sp_chs); add(sp_ch);
-        add(sp_ass); add(sp_as); add(sp_lv); add(sp_off); add(sp_roff); add(dgoff); add(dstatus); add(dctl); add(drec);
+        add(dX); add(dZi); add(dInfo); add(dErec); add(dEchi); add(dHblk); add(db); add(dG); add(dOut); add(dei); add(dej); add(dbs);
+        add(dbsrc); add(dbdiag); add(dbrow); add(dplace); add(dpar); add(dgoff); add(dstatus); add(dctl); add(drec);
     }
     if (n > 0) {
         hipLaunchKernelGGL(k_pgo_edges<true>, dim3((unsigned)((std::max(ne, 1) + 63) / 64)), dim3(64), 0, s, d);
         hipLaunchKernelGGL(k_pgo_sum, dim3((unsigned)((std::max(nblk, 1) + 3) / 4)), dim3(256), 0, s, d);
         pgo_sparse_launch_assemble(sd, plan, s);
-        for (int l = 0; l < plan.nlev; ++l) pgo_sparse_launch_factor(sd, plan.lv_start[l], plan.lv_start[l + 1] - plan.lv_start[l], s);
+        pgo_sparse_launch_factor_levels(sd, plan, s);
     }
     pgo_cov_launch(sd, cd, plan, s);      // (nothing to invert without a free vertex: the zeros and NaNs of the statuses alone)
     HIPCK(p, hipMemcpyAsync(dOut.p, dctl.p, sizeof(PgoCtl), hipMemcpyDeviceToDevice, s));
@@ -814,8 +789,7 @@ int plba_pose_graph_marginals(plba_problem* p, const plba_pose_graph* g, plba_pg
         if (m->pair_status) memcpy(m->pair_status, status.data() + it0, (size_t)npairs);
     }
     for (int i = 0; i < 4; ++i) m->n_status[i] = n_status[i];
-    p->pgo_cov[0] = 1.0; p->pgo_cov[1] = n; p->pgo_cov[2] = plan.nfront; p->pgo_cov[3] = plan.nlev; p->pgo_cov[4] = (double)plan.nnz_blk; p->pgo_cov[5] = plan.max_m;
-    p->pgo_cov[6] = (double)bytes; p->pgo_cov[7] = ms_analysis;
+    pgo_sparse_record(p->pgo_cov, n, plan, bytes, ms_analysis);
     return PLBA_OK;
 }
 

@@ -9,7 +9,7 @@
 
 #include "plba_internal.h"
 #include "plba_pgo_cov.h"
-#include "plba_pgo_sparse.h"
+#include "plba_pgo_sparse_dev.h"
 
 namespace plba {
 namespace {

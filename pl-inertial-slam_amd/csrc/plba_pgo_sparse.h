@@ -16,13 +16,14 @@
 //   k_sps_back       per level, top-down: L11^T x1 = y1 - L21^T x2 with x2 gathered from the ancestors      workgroup per front
 // Front f keeps its m x m frontal matrix column-major (lower triangle used) at F + f_off[f] and its right-hand side at R + f_roff[f];
 // nothing of size n x n exists on either side.
+// Standard library only (plba_pgo_cov_hostcheck.cpp builds over it with a plain C++ compiler); the device side, which plba_lba_visual
+// (solver = 1) and plba_pose_graph_marginals use as well, is plba_pgo_sparse_dev.h.
 #pragma once
 #include <algorithm>
+#include <cstddef>
 #include <cstdint>
 #include <numeric>
 #include <vector>
-
-#include "plba_internal.h"
 
 namespace plba {
 
@@ -40,25 +41,11 @@ struct PgoSparsePlan {
     long long fsize = 0, rsize = 0;
 };
 
-// what the kernels read (device pointers)
-struct PgoSparseDev {
-    const int32_t *f_m, *f_np, *f_row0, *rows, *umap, *ch_start, *ch, *as_start, *as, *lv;
-    const long long *f_off, *f_roff;
-    double* F;                  // frontal matrices
-    double* R;                  // their right-hand sides
-    const double* Hblk;         // nblk x 36, undamped
-    const double* b;            // P
-    double* x;                  // P, free-vertex order
-    Ctrl* c;                    // lambda in, solver_ok out
-    const int* done;            // PgoCtl::done
-};
-#ifdef __HIPCC__
-void pgo_sparse_launch(const PgoSparseDev& d, const PgoSparsePlan& pl, hipStream_t s);      // one trial's solve
-// its first two stages on their own (plba_pose_graph_marginals factors and then inverts): k_sps_assemble over every front, and
-// k_sps_factor over the fronts lv[l0 .. l0 + count) of one level
-void pgo_sparse_launch_assemble(const PgoSparseDev& d, const PgoSparsePlan& pl, hipStream_t s);
-void pgo_sparse_launch_factor(const PgoSparseDev& d, int l0, int count, hipStream_t s);
-#endif
+// the record every caller of the solver keeps for plba_debug_get ("pgo_sparse", "lba_sparse", "pgo_cov"; include/plba.h):
+// 1, n, fronts, levels, nonzero blocks of L, largest front, device bytes of the call's buffers, ms of the host analysis
+inline void pgo_sparse_record(double rec[8], int n, const PgoSparsePlan& pl, size_t bytes, double ms) {
+    rec[0] = 1.0; rec[1] = n; rec[2] = pl.nfront; rec[3] = pl.nlev; rec[4] = (double)pl.nnz_blk; rec[5] = pl.max_m; rec[6] = (double)bytes; rec[7] = ms;
+}
 
 // blk_row / blk_col: the free ranks of every block of H (row >= column); diagonal blocks exist for every free rank.
 // false: the plan failed its own index checks (every index the kernels form is checked here, before anything is launched)

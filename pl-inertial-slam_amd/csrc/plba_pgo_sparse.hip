@@ -1,5 +1,5 @@
 // plba_pgo_sparse.hip — the multifrontal solve of plba_optimize_pose_graph's sparse path (options.pgo_solver = 1); the host analysis,
-// the layout and the kernel sequence are described in plba_pgo_sparse.h.
+// the layout and the kernel sequence are described in plba_pgo_sparse.h; PgoSparseDev and the launchers are declared in plba_pgo_sparse_dev.h.
 // One workgroup of 256 per front.  A frontal matrix lives in global memory (L2-resident for the fronts of a keyframe chain; fronts of
 // any size, a fully connected graph's included, take the same path).  Every entry has one owner and every sum a fixed order: the
 // extend-add runs child by child with a barrier between, the pivot columns and the trailing update F22 - L21 L21^T sum over k in
@@ -7,8 +7,7 @@
 // Every kernel returns at once after the run has ended (PgoCtl::done).
 #include <cmath>
 
-#include "plba_internal.h"
-#include "plba_pgo_sparse.h"
+#include "plba_pgo_sparse_dev.h"
 
 namespace plba {
 namespace {
@@ -218,9 +217,13 @@ void pgo_sparse_launch_factor(const PgoSparseDev& d, int l0, int count, hipStrea
     hipLaunchKernelGGL(k_sps_factor, dim3((unsigned)count), dim3(SPT), 0, s, d, l0);
 }
 
+void pgo_sparse_launch_factor_levels(const PgoSparseDev& d, const PgoSparsePlan& pl, hipStream_t s) {
+    for (int l = 0; l < pl.nlev; ++l) pgo_sparse_launch_factor(d, pl.lv_start[l], pl.lv_start[l + 1] - pl.lv_start[l], s);
+}
+
 void pgo_sparse_launch(const PgoSparseDev& d, const PgoSparsePlan& pl, hipStream_t s) {
     pgo_sparse_launch_assemble(d, pl, s);
-    for (int l = 0; l < pl.nlev; ++l) pgo_sparse_launch_factor(d, pl.lv_start[l], pl.lv_start[l + 1] - pl.lv_start[l], s);
+    pgo_sparse_launch_factor_levels(d, pl, s);
     for (int l = pl.nlev - 1; l >= 0; --l)
         hipLaunchKernelGGL(k_sps_back, dim3((unsigned)(pl.lv_start[l + 1] - pl.lv_start[l])), dim3(SPT), 0, s, d, pl.lv_start[l]);
 }

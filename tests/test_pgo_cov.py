@@ -151,6 +151,24 @@ def test_determinism_and_isolation(pkg, orc, hip):
         assert np.array_equal(_bits(x[1]), _bits(y[1])) and x[2] == y[2] and x[3] == y[3] and x[4] == y[4]
 
 
+def test_the_optimiser_and_the_marginals_hold_the_same_plan(pkg, orc, hip):
+    """one analysis and one device image of it behind both entry points: free vertices, fronts, levels, blocks of L and the largest front
+    of the two records agree exactly (the bytes differ: each call counts its own buffers besides)"""
+    g = pgo_ref.cov_graph(40, seed=3)
+    p = pkg.new_problem(pgo_solver=1)
+    try:
+        p.pgo(g["pose"], g["ei"], g["ej"], g["meas"], info=g["info"], fixed=g["fixed"], iters=1, user_lambda=LAM)
+        opt = p.debug_get("pgo_sparse").copy()
+        p.pgo_marginals(g["pose"], g["ei"], g["ej"], g["meas"], info=g["info"], fixed=g["fixed"])
+        cov = p.debug_get("pgo_cov").copy()
+    finally:
+        p.close()
+    print("pgo_sparse", opt, "pgo_cov", cov)
+    assert opt[0] == 1 and cov[0] == 1 and opt[1] == 38
+    assert np.array_equal(opt[1:6], cov[1:6]), (opt, cov)
+    assert opt[6] > 0 and cov[6] > 0
+
+
 def test_the_call_blocks_once(pkg, orc, hip):
     """the header's count of blocking waits, by plba_debug_get("host_waits"): one read-back; one more for the dump; one more to name the
     front of a failed factorisation"""

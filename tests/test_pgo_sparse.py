@@ -150,6 +150,8 @@ def test_structures_sparse_against_dense(pkg, orc, hip, name):
     assert np.array_equal(X[keep], g["pose"][keep]) and np.array_equal(X3[keep], g["pose"][keep])
     if name == "complete80":
         assert info[2] == 1 and info[5] == 6 * 79                               # one front, wider than LDS holds
+    if name == "one_free":
+        assert info[2] == 1 and info[5] == 6                                    # one front without children: the plan's child list is empty
     assert info[1] == (touched & ~g["fixed"].astype(bool)).sum()
 
 
