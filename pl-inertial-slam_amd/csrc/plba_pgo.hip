@@ -35,6 +35,7 @@
 
 #include "plba_internal.h"
 #include "plba_pgo_cov.h"
+#include "plba_pgo_dev.h"
 #include "plba_pgo_sparse_dev.h"
 #include "plba_problem.h"
 
@@ -44,8 +45,7 @@
 namespace plba {
 namespace {
 
-constexpr int PGO_REC = 120;          // per-edge record (see the layout above)
-constexpr int ORTHO_AFTER = 1000;  // VertexSE3::orthogonalizeAfter
+using namespace pgo_dev;      // the per-edge evaluation and the per-vertex update (plba_pgo_dev.h)
 
 // device-side control: the Ctrl the factorisation reports solver_ok into, + the loop state of optimizeHost
 struct PgoCtl {
@@ -85,122 +85,21 @@ struct PgoDev {
     plba_trace_row* trace;
 };
 
-struct Iso { M3 R; V3 t; };
-__device__ __forceinline__ Iso iso_load(const double* p) {
-    Iso a;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) a.R.a[i] = p[i];
-    a.t = v3(p[9], p[10], p[11]);
-    return a;
-}
-__device__ __forceinline__ void iso_store(const Iso& a, double* p) {
-#pragma unroll
-    for (int i = 0; i < 9; ++i) p[i] = a.R.a[i];
-    p[9] = a.t.x; p[10] = a.t.y; p[11] = a.t.z;
-}
-// slam3d_detail::mul / inv / from_mqt / unit_q of include/plba_g2o/types_slam3d.h, on the plba_math.h helpers
-__device__ __forceinline__ Iso iso_mul(const Iso& a, const Iso& b) { Iso r; r.R = mul(a.R, b.R); r.t = mul(a.R, b.t) + a.t; return r; }
-__device__ __forceinline__ Iso iso_inv(const Iso& a) { Iso r; r.R = transpose(a.R); const V3 x = mul(r.R, a.t); r.t = v3(-x.x, -x.y, -x.z); return r; }
-__device__ __forceinline__ Iso iso_from_mqt(const double* u) {
-    Iso r;
-    r.t = v3(u[0], u[1], u[2]);
-    const double w2 = 1.0 - (u[3] * u[3] + u[4] * u[4] + u[5] * u[5]);
-    if (w2 < 0) r.R = eye3();
-    else { Q4 q; q.x = u[3]; q.y = u[4]; q.z = u[5]; q.w = sqrt(w2); r.R = q_to_R(q); }
-    return r;
-}
-__device__ __forceinline__ Q4 unit_q(const M3& R) {
-    Q4 q = q_normalized(R_to_q(R));
-    if (q.w < 0) { q.x = -q.x; q.y = -q.y; q.z = -q.z; q.w = -q.w; }
-    return q;
-}
-
-// EdgeSE3::computeError (+ linearizeOplus and the weighted blocks of buildHost when JAC)
+// EdgeSE3::computeError (+ linearizeOplus and the weighted blocks of buildHost when JAC), a thread per edge: the text pgo_edge_eval
+// (plba_pgo_dev.h) runs on the host, included here and not called so that the kernel's FMA pairing, and with it every bit, stays as it was
 template <bool JAC>
 __global__ __launch_bounds__(64) void k_pgo_edges(PgoDev d) {
     if (d.ctl->done || (JAC && !d.ctl->lin)) return;
     const int k = blockIdx.x * 64 + threadIdx.x;
     if (k >= d.ne) return;
     const Iso Xi = iso_load(d.X + (size_t)12 * d.ei[k]), Xj = iso_load(d.X + (size_t)12 * d.ej[k]), Zi = iso_load(d.Zi + (size_t)12 * k);
-    const double* om = d.info + (size_t)36 * k;
-    const Iso E = iso_mul(iso_mul(Zi, iso_inv(Xi)), Xj);
-    const Q4 qe = unit_q(E.R);
-    const double e[6] = {E.t.x, E.t.y, E.t.z, qe.x, qe.y, qe.z};
-    double we[6], chi = 0.0;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double t = 0.0;
-#pragma unroll
-        for (int j = 0; j < 6; ++j) t += om[i * 6 + j] * e[j];
-        we[i] = t;
-        chi += e[i] * t;
-    }
-    d.echi[k] = chi;
-    if (!JAC) return;
-    // linearizeOplus: E = Z^-1 (Xi^-1 Xj) = Zi B, q its unit quaternion; derivation next to EdgeSE3::linearizeOplus
-    const Iso B = iso_mul(iso_inv(Xi), Xj), E2 = iso_mul(Zi, B);
-    const Q4 q = unit_q(E2.R);
-    const M3 RZt = Zi.R, V = hat(v3(q.x, q.y, q.z)), TB = hat(B.t), RZtTB = mul(RZt, TB);
-    M3 Qm, Qp;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) { const double dg = (i % 4 == 0) ? q.w : 0.0; Qm.a[i] = dg - V.a[i]; Qp.a[i] = dg + V.a[i]; }
-    const M3 QmRZt = mul(Qm, RZt);
-    double J0[36], J1[36];
-#pragma unroll
-    for (int i = 0; i < 36; ++i) { J0[i] = 0.0; J1[i] = 0.0; }
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            J0[r * 6 + c] = -RZt.a[r * 3 + c];
-            J0[r * 6 + 3 + c] = 2.0 * RZtTB.a[r * 3 + c];
-            J0[(3 + r) * 6 + 3 + c] = -QmRZt.a[r * 3 + c];
-            J1[r * 6 + c] = E2.R.a[r * 3 + c];
-            J1[(3 + r) * 6 + 3 + c] = Qp.a[r * 3 + c];
-        }
-    double* rec = d.erec + (size_t)PGO_REC * k;
-    // g_a = J_a^T O e  (b -= g_a in the sum)
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-        double t0 = 0.0, t1 = 0.0;
-#pragma unroll
-        for (int r = 0; r < 6; ++r) { t0 += J0[r * 6 + c] * we[r]; t1 += J1[r * 6 + c] * we[r]; }
-        rec[108 + c] = t0; rec[114 + c] = t1;
-    }
-    // O J0 -> A00 = J0^T (O J0), A10 = J1^T (O J0); then O J1 -> A11
-    double OJ[36];
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-        for (int c = 0; c < 6; ++c) { double t = 0.0;
-#pragma unroll
-            for (int q2 = 0; q2 < 6; ++q2) t += om[r * 6 + q2] * J0[q2 * 6 + c];
-            OJ[r * 6 + c] = t; }
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-        for (int c = 0; c < 6; ++c) {
-            double t0 = 0.0, t1 = 0.0;
-#pragma unroll
-            for (int q2 = 0; q2 < 6; ++q2) { t0 += J0[q2 * 6 + r] * OJ[q2 * 6 + c]; t1 += J1[q2 * 6 + r] * OJ[q2 * 6 + c]; }
-            rec[r * 6 + c] = t0; rec[72 + r * 6 + c] = t1;
-        }
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-        for (int c = 0; c < 6; ++c) { double t = 0.0;
-#pragma unroll
-            for (int q2 = 0; q2 < 6; ++q2) t += om[r * 6 + q2] * J1[q2 * 6 + c];
-            OJ[r * 6 + c] = t; }
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-        for (int c = 0; c < 6; ++c) {
-            double t = 0.0;
-#pragma unroll
-            for (int q2 = 0; q2 < 6; ++q2) t += J1[q2 * 6 + r] * OJ[q2 * 6 + c];
-            rec[36 + r * 6 + c] = t;
-        }
+#define PGO_EDGE_OM (d.info + (size_t)36 * k)
+#define PGO_EDGE_CHI d.echi[k]
+#define PGO_EDGE_REC (d.erec + (size_t)PGO_REC * k)
+#include "plba_pgo_edge_body.inc"
+#undef PGO_EDGE_OM
+#undef PGO_EDGE_CHI
+#undef PGO_EDGE_REC
 }
 
 // Hblk, b: a wave per block, lane l < 36 owns entry l, lanes 36..41 the block's b (diagonal blocks); sources in edge order
@@ -215,8 +114,7 @@ __global__ __launch_bounds__(256) void k_pgo_sum(PgoDev d) {
         const int src = d.blk_src[s], k = src >> 2, slot = src & 3;
         const double* rec = d.erec + (size_t)PGO_REC * k;
         if (l >= 36) acc -= rec[(slot == 0 ? 108 : 114) + r];
-        else if (slot == 3) acc += rec[72 + c * 6 + r];
-        else acc += rec[slot * 36 + r * 6 + c];
+        else acc += pgo_block_term(rec, slot, r, c);
     }
     if (l < 36) d.Hblk[(size_t)36 * blk + l] = acc;
     else d.b[6 * d.blk_row[blk] + r] = acc;
@@ -301,16 +199,7 @@ __global__ __launch_bounds__(64) void k_pgo_update(PgoDev d) {
     const bool ok = d.ctl->c.solver_ok != 0;      // a failed factorisation: the host path's x = 0
 #pragma unroll
     for (int i = 0; i < 6; ++i) u[i] = ok ? d.x[6 * k + i] : 0.0;
-    Iso X = iso_mul(iso_load(xp), iso_from_mqt(u));
-    if (++d.cnt[v] > ORTHO_AFTER) {      // approximateNearestOrthogonalMatrix: R -= 0.5 R (R^T R - I)
-        d.cnt[v] = 0;
-        M3 E = mulAtB(X.R, X.R);
-        E.a[0] -= 1; E.a[4] -= 1; E.a[8] -= 1;
-        const M3 RE = mul(X.R, E);
-#pragma unroll
-        for (int i = 0; i < 9; ++i) X.R.a[i] -= 0.5 * RE.a[i];
-    }
-    iso_store(X, xp);
+    pgo_vertex_oplus(xp, u, d.cnt + v);
 }
 
 __device__ void pgo_deliver(const PgoDev& d, unsigned long long seq) {
