@@ -1442,7 +1442,7 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
     }
     lap("chain maps + buffers");
     d.Ninv = nullptr; d.Nwork = nullptr;
-    HIPCK(p, p->d_dbgbuf.alloc(128)); d.dbgbuf = p->d_dbgbuf.p; p->dd.dbgbuf = d.dbgbuf;
+    HIPCK(p, p->d_dbgbuf.alloc(DBGBUF_N)); d.dbgbuf = p->d_dbgbuf.p; p->dd.dbgbuf = d.dbgbuf;
     if (!p->chain_ok && p->P > 0 && ninv_fits(p->Ppad)) { HIPCK(p, p->work.alloc_ninv(p->Ppad, p->ld)); p->work.bind_ninv(d); }
     // ---- structural assembly list (assemble_part): with the chain elimination on, sys is written by the assembly pass and
     // by k_schur_pairs only, so the entries neither of them can make non-zero never need touching again
@@ -2755,7 +2755,7 @@ int plba_debug_get(plba_problem* p, const char* what, double* out, size_t cap, s
         HIPCK(p, fetch(d.erec, ((size_t)p->win.Ep + 2 * (size_t)p->win.El) * EREC_UNIT, v));
     }
     else if (w == "stamps") { HIPCK(p, fetch(d.maxd_part, 80, v)); }
-    else if (w == "dbgbuf") { HIPCK(p, fetch(d.dbgbuf, 128, v)); }
+    else if (w == "dbgbuf") { HIPCK(p, fetch(d.dbgbuf, DBGBUF_N, v)); }
     else if (w == "pose_dim") v = {(double)p->P};
     else if (w == "marg_path") v.assign(p->marg_path, p->marg_path + 5);
     else if (w == "prof_lin_launches") v = {(double)p->prof_lin_launches};

@@ -135,6 +135,15 @@ struct DevBuf {  // trivially-copyable view of device pointers passed to kernels
     int* trace_n;
 };
 
+// DevBuf::dbgbuf: 128 doubles of cycle stamps.  The PLBA_STAMPS_LMF build appends one record per workgroup of k_lm_schur<0> and of
+// k_lm_trial<true> (tools/stamps_lmf.py --wg): [start tick, end tick, HW_ID, XCC_ID, kind] at DBG_WG_BASE + DBG_WG_REC * (DBG_WG_MAX * launch + block)
+constexpr int DBG_WG_BASE = 128, DBG_WG_REC = 5, DBG_WG_MAX = 1024;
+#ifdef PLBA_STAMPS_LMF
+constexpr int DBGBUF_N = DBG_WG_BASE + 2 * DBG_WG_REC * DBG_WG_MAX;
+#else
+constexpr int DBGBUF_N = 128;
+#endif
+
 struct Robust { int on[5]; double delta[5]; };
 
 // ---- fused landmark-major passes (plba_lm_dev.h): group structure built at upload ---------------------------------------------

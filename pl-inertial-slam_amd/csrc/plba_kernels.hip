@@ -1669,6 +1669,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     __shared__ LmLds S;
     extern __shared__ __attribute__((aligned(16))) double s_dyn_lm[];      // LmAcc (36 KB) | a chain segment's staging (48 KB)
     int b = blockIdx.x;
+#ifdef PLBA_STAMPS_LMF
+    LmWgStamp wgs(d, 0, MODE == 0);
+    if (MODE == 0) { if (b < nlead) wgs.kind = -1; else wgs.group(lv.grp[b - nlead]); }
+#endif
     if (MODE == 0 && b < nlead) { chain_elim_segment<true>(d, cv, b, *reinterpret_cast<ChainElimLds*>(s_dyn_lm)); return; }
     b -= nlead;
     if (MODE == 1 && b >= lv.ngrp) {      // first iteration of a call: the pose-side edges (with Jacobians) ride behind the groups instead of in a launch of their own
@@ -1723,6 +1727,13 @@ __global__ __launch_bounds__(LMB) void k_lm_trial(DevBuf d, LmView lv, int cur, 
     // configs[4] (1183 workgroups, two rounds of groups) 200 edge blocks at the head delay the first round of groups — 0.4257 -> 0.4310 —
     // and stay at the tail, where they fill the slots the second round leaves free.
     const int nimu_first = (nlead > 0 && npose > 0 && cv.imu_loc && gridDim.x <= 512) ? min(npose, d.M) : 0;
+#ifdef PLBA_STAMPS_LMF
+    LmWgStamp wgs(d, 1, JAC);
+    if (b < nlead) wgs.kind = -1;
+    else if (b < nlead + nimu_first) wgs.kind = -2;
+    else if (b - nimu_first < nlead + lv.ngrp) wgs.group(lv.grp[b - nimu_first - nlead]);
+    else wgs.kind = (b - nlead - lv.ngrp < d.M) ? -2 : -3;
+#endif
     if (b >= nlead && b < nlead + nimu_first) {
         const LocalStates loc{&cv, xd, cur};
         pose_edge_block<JAC, 256>(d, trial, rb, b - nlead, threadIdx.x, nullptr, 0, s4, nullptr, &loc);

@@ -160,11 +160,16 @@ DEV void lm_lowerT_mul(const double* Li, const double* v, double* o) {     // o 
 struct LmStep {      // one lane's share of a step's inputs (prefetched a step ahead)
     int slot, k, e, ws, orig;      // ws: the window slot of this lane (= lane & 7: the 8 lanes of a unit ARE the 8 slots, with or without an observation,
                                    // so the operand never needs clearing)
-    bool uvalid, has, lvl0, fixed;
+    bool uvalid, has, fixed;
+    int lvl;                       // the observation's level as loaded (0: active); compared where it is used, so that the load is not waited for here
     double meas[3], wt, L[6];
 };
 // the loads of a step come in two dependent levels: the unit's indices (LmIdx), then its landmark and its lane's observation
-struct LmIdx { int slot, e; bool uvalid, has, fixed; };
+// (held AS LOADED — the slot byte, the landmark's first observation, the fixed flag — and turned into has / e / fixed by lm_load_data a step
+// later: a comparison made here made the compiler wait for each of these loads before it issued the next, three dependent round trips per step
+// in front of the matrix phase)
+struct LmIdx { int slot, ob0, off, fix; bool uvalid; };
+DEV void lm_idx_none(LmIdx& x) { x.uvalid = false; x.slot = 0; x.ob0 = 0; x.off = 0xFF; x.fix = 1; }
 // WIDE: a landmark block takes TWO neighbouring units — window slots 0 - 7 and 8 - 15 — so a point is 2 units and a line 4
 // (end point P: slots 0 - 7 | 8 - 15, then end point Q likewise); the lane's window slot is 8 (unit & 1) + (lane & 7)
 // The group descriptor is NOT copied into a local: its window arrays are indexed by the thread (g.kf[p]), which put the whole struct into
@@ -177,18 +182,18 @@ template <bool IS_LINE, bool WIDE = false>
 DEV void lm_load_idx(const LmView& lv, const LmHead& g, int step, int wv, int lane, LmIdx& x) {
     const int unit = step * LMF_UNITS + wv * 8 + (lane >> 3), sub = WIDE ? 8 * ((lane >> 3) & 1) + (lane & 7) : (lane & 7);
     const int n = WIDE ? (IS_LINE ? (unit >> 2) : (unit >> 1)) : (IS_LINE ? (unit >> 1) : unit);
-    x.uvalid = n < g.nlm; x.slot = 0; x.e = 0; x.has = false; x.fixed = true;
+    lm_idx_none(x);
+    x.uvalid = n < g.nlm;
     if (!x.uvalid) return;
     const int gi = g.lm0 + n;
     x.slot = lv.lm_grouped ? gi : lv.lm_slot[gi];      // the landmark's place in DevBuf::lm (grouped storage: its place in the group tables)
-    const int off = lv.lm_ws8[(size_t)gi * lv.wmax + sub];      // lane = window slot
-    x.has = off != 0xFF;
-    x.e = lv.lm_ob0[gi] + (x.has ? off : 0);
-    x.fixed = lv.lm_fixed_g[gi] != 0;
+    x.off = lv.lm_ws8[(unsigned)(gi * lv.wmax + sub)];      // lane = window slot; 0xFF: no observation (a 32-bit offset from the table's base: no per-lane pointer to keep)
+    x.ob0 = lv.lm_ob0[gi];
+    x.fix = lv.lm_fixed_g[gi];
 }
 template <bool IS_LINE, bool WIDE = false>
 DEV void lm_load_data(const DevBuf& d, const LmView& lv, int state, int lane, const LmIdx& x, LmStep& s) {
-    s.uvalid = x.uvalid; s.slot = x.slot; s.k = 0; s.e = x.e; s.ws = WIDE ? 8 * ((lane >> 3) & 1) + (lane & 7) : (lane & 7); s.orig = 0; s.has = x.has; s.lvl0 = false; s.fixed = x.fixed; s.wt = 0.0;
+    s.uvalid = x.uvalid; s.slot = x.slot; s.k = 0; s.has = x.off != 0xFF; s.e = x.ob0 + (s.has ? x.off : 0); s.ws = WIDE ? 8 * ((lane >> 3) & 1) + (lane & 7) : (lane & 7); s.orig = 0; s.lvl = 1; s.fixed = x.fix != 0; s.wt = 0.0;
 #pragma unroll
     for (int t = 0; t < 3; ++t) s.meas[t] = 0.0;
 #pragma unroll
@@ -199,7 +204,7 @@ DEV void lm_load_data(const DevBuf& d, const LmView& lv, int state, int lane, co
     if (IS_LINE) { s.L[3] = Lp[3]; s.L[4] = Lp[4]; s.L[5] = Lp[5]; }
     if (s.has) {
         s.orig = lv.ob_err ? lv.ob_orig[s.e] : 0; s.wt = lv.ob_wt[s.e];      // (the original index: only the parity tests' residual dump needs it)
-        s.lvl0 = lv.ob_level_g[s.e] == 0;
+        s.lvl = lv.ob_level_g[s.e];
         if (IS_LINE) { const double* m = lv.meas_ln + (size_t)(s.e - d.Ep) * 3; s.meas[0] = m[0]; s.meas[1] = m[1]; s.meas[2] = m[2]; }
         else { const double2 m = reinterpret_cast<const double2*>(lv.meas_pt)[s.e]; s.meas[0] = m.x; s.meas[1] = m.y; }
     }
@@ -238,6 +243,29 @@ DEV void lm_wave_sync() {
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
+#ifdef PLBA_STAMPS_LMF
+// diagnostic build only: where and when every workgroup of a launch ran.  Declared at the top of k_lm_schur<0> / k_lm_trial<true>; wave 0's
+// lane 0 writes the record when the kernel body returns, on whichever path.  kind: steps of a point group, 100 + steps of a line group,
+// -1 chain segment, -2 IMU edge block, -3 prior block.  HW_ID (register 4): wave [3:0], SIMD [5:4], CU [11:8], SH [12], SE [15:13];
+// XCC_ID (register 20): [3:0].
+struct LmWgStamp {
+    double* rec; long long t0; int kind;
+    DEV LmWgStamp(const DevBuf& d, int launch, bool on) : rec(nullptr), kind(0) {
+        t0 = (long long)__builtin_amdgcn_s_memrealtime();
+        if (!on) return;
+        if ((int)blockIdx.x < DBG_WG_MAX) rec = d.dbgbuf + DBG_WG_BASE + DBG_WG_REC * (DBG_WG_MAX * launch + (int)blockIdx.x);
+        if (blockIdx.x == 0 && threadIdx.x == 0) d.dbgbuf[126 + launch] = (double)gridDim.x;
+    }
+    DEV void group(const LmGroup& g) { const int st = (((g.kind & 1) ? 2 * g.nlm : g.nlm) * ((g.kind & 2) ? 2 : 1) + 31) / 32; kind = ((g.kind & 1) ? 100 : 0) + st; }
+    DEV ~LmWgStamp() {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (rec && threadIdx.x == 0) {
+            rec[0] = (double)t0; rec[1] = (double)(long long)__builtin_amdgcn_s_memrealtime();
+            rec[2] = (double)__builtin_amdgcn_s_getreg(4 | (31 << 11)); rec[3] = (double)__builtin_amdgcn_s_getreg(20 | (3 << 11)); rec[4] = (double)kind;
+        }
+    }
+};
+#endif
 template <bool IS_LINE, int MODE>
 DEV void lm_schur_group(const DevBuf& d, const LmView& lv, const int gidx, const int state, const Robust& rb, LmLds& S, LmAcc& A4) {
     constexpr int NR = IS_LINE ? 1 : 2;
@@ -259,7 +287,7 @@ DEV void lm_schur_group(const DevBuf& d, const LmView& lv, const int gidx, const
     LmStep cur;
     lm_load<IS_LINE>(d, lv, g, state, 0, wv, lane, cur);
     LmIdx ix1;      // indices of step + 1 (a step ahead of the data they lead to: the two levels of loads never wait for each other)
-    ix1.uvalid = false; ix1.slot = 0; ix1.e = 0; ix1.has = false; ix1.fixed = true;
+    lm_idx_none(ix1);
     if (nsteps > 1) lm_load_idx<IS_LINE>(lv, g, 1, wv, lane, ix1);
     __syncthreads();
     const double* kc = S.kc[0][sub];
@@ -275,7 +303,7 @@ DEV void lm_schur_group(const DevBuf& d, const LmView& lv, const int gidx, const
         FSTAMP(1);
         LmRows<NR> r;
         const int rowsel = IS_LINE ? (u8 & 1) : 0;
-        lm_eval<IS_LINE, NR>(d, rb, kc, cur.has && kfree, cur.L, cur.meas, cur.wt, cur.has, cur.lvl0, rowsel, true, r);
+        lm_eval<IS_LINE, NR>(d, rb, kc, cur.has && kfree, cur.L, cur.meas, cur.wt, cur.has, cur.lvl == 0, rowsel, true, r);
         FSTAMP(2);
         double h[6], b[3];
         int nact;
@@ -362,11 +390,21 @@ DEV void lm_schur_group(const DevBuf& d, const LmView& lv, const int gidx, const
             FSTAMP(4);
             // the next step's inputs are requested HERE — this step's evaluation is over, so its registers are free — and arrive during the
             // matrix phase; the indices of the step after that ride along
+            // (both unconditionally: past the group's end ix1 is "none" and nothing is loaded — behind a branch the compiler had to assume the
+            // previous indices still in flight and waited for THIS step's data loads before it touched ix1 again)
             LmStep nxt;
-            if (step + 1 < nsteps) lm_load_data<IS_LINE>(d, lv, state, lane, ix1, nxt);
+            lm_load_data<IS_LINE>(d, lv, state, lane, ix1, nxt);
             if (step + 2 < nsteps) lm_load_idx<IS_LINE>(lv, g, step + 2, wv, lane, ix1);
+            else lm_idx_none(ix1);
             lm_wave_sync();
             // ---- rank-24 update of the wave's six lower tiles ----
+            // Only the tile pairs whose two 16-row blocks hold an observation this step: a window slot none of the wave's 8 units observes
+            // from is six zero rows of the panel (every lane writes its slot's rows, with or without an observation), and a product of two
+            // zero blocks adds +0 to a tile — skipping it leaves every bit as it was.  rows 0 - 15: slots 0 - 2, 16 - 31: slots 2 - 5,
+            // 32 - 47: slots 5 - 7.  The mask is a ballot, wave-uniform: scalar branches, no exec-masked MFMA.
+            const unsigned long long hb = __builtin_amdgcn_ballot_w64(cur.has);
+            const unsigned h32 = (unsigned)hb | (unsigned)(hb >> 32), h8 = (h32 | (h32 >> 8) | (h32 >> 16) | (h32 >> 24)) & 0xFFu;
+            const bool rb0 = (h8 & 0x07u) != 0, rb1 = (h8 & 0x3Cu) != 0, rb2 = (h8 & 0xE0u) != 0;
 #pragma unroll 2
             for (int s4 = 0; s4 < LMF_WCOLS / 4; ++s4) {
                 const double* col = op + (4 * s4 + lk) * LMF_ROWS + li;
@@ -375,12 +413,16 @@ DEV void lm_schur_group(const DevBuf& d, const LmView& lv, const int gidx, const
                 a00[0] += f0 * f1 * f2;
                 continue;
 #endif
-                a00 = __builtin_amdgcn_mfma_f64_16x16x4f64(f0, f0, a00, 0, 0, 0);
-                a10 = __builtin_amdgcn_mfma_f64_16x16x4f64(f1, f0, a10, 0, 0, 0);
-                a11 = __builtin_amdgcn_mfma_f64_16x16x4f64(f1, f1, a11, 0, 0, 0);
-                a20 = __builtin_amdgcn_mfma_f64_16x16x4f64(f2, f0, a20, 0, 0, 0);
-                a21 = __builtin_amdgcn_mfma_f64_16x16x4f64(f2, f1, a21, 0, 0, 0);
-                a22 = __builtin_amdgcn_mfma_f64_16x16x4f64(f2, f2, a22, 0, 0, 0);
+                if (rb0) a00 = __builtin_amdgcn_mfma_f64_16x16x4f64(f0, f0, a00, 0, 0, 0);
+                if (rb1) {
+                    if (rb0) a10 = __builtin_amdgcn_mfma_f64_16x16x4f64(f1, f0, a10, 0, 0, 0);
+                    a11 = __builtin_amdgcn_mfma_f64_16x16x4f64(f1, f1, a11, 0, 0, 0);
+                }
+                if (rb2) {
+                    if (rb0) a20 = __builtin_amdgcn_mfma_f64_16x16x4f64(f2, f0, a20, 0, 0, 0);
+                    if (rb1) a21 = __builtin_amdgcn_mfma_f64_16x16x4f64(f2, f1, a21, 0, 0, 0);
+                    a22 = __builtin_amdgcn_mfma_f64_16x16x4f64(f2, f2, a22, 0, 0, 0);
+                }
             }
             FSTAMP(5);
             lm_wave_sync();      // (the next step's operand writes stay behind these reads)
@@ -507,7 +549,7 @@ DEV void lm_schur_group_wide(const DevBuf& d, const LmView& lv, const int gidx, 
     LmStep cur;
     lm_load<IS_LINE, true>(d, lv, g, state, 0, wv, lane, cur);
     LmIdx ix1;
-    ix1.uvalid = false; ix1.slot = 0; ix1.e = 0; ix1.has = false; ix1.fixed = true;
+    lm_idx_none(ix1);
     if (nsteps > 1) lm_load_idx<IS_LINE, true>(lv, g, 1, wv, lane, ix1);
     __syncthreads();
     const double* kc = S.kc[0][slot];
@@ -531,7 +573,7 @@ DEV void lm_schur_group_wide(const DevBuf& d, const LmView& lv, const int gidx, 
     for (int step = 0; step < nsteps; ++step) {
         LmRows<NR> r;
         const int rowsel = IS_LINE ? (blk & 1) : 0;
-        lm_eval<IS_LINE, NR>(d, rb, kc, cur.has && kfree, cur.L, cur.meas, cur.wt, cur.has, cur.lvl0, rowsel, true, r);
+        lm_eval<IS_LINE, NR>(d, rb, kc, cur.has && kfree, cur.L, cur.meas, cur.wt, cur.has, cur.lvl == 0, rowsel, true, r);
         double h[6], b[3];
         int nact;
         lm_hll<NR, true>(r, h, b, nact);
@@ -818,14 +860,14 @@ DEV void lm_trial_group(const DevBuf& d, const LmView& lv, const int gidx, const
     LmStep cur;
     lm_load<IS_LINE, WIDE>(d, lv, g, cur_state, 0, wv, lane, cur);
     LmIdx ix1;      // indices of step + 1, a step ahead of the data they lead to (see lm_schur_group)
-    ix1.uvalid = false; ix1.slot = 0; ix1.e = 0; ix1.has = false; ix1.fixed = true;
+    lm_idx_none(ix1);
     if (nsteps > 1) lm_load_idx<IS_LINE, WIDE>(lv, g, 1, wv, lane, ix1);
     __syncthreads();
     double chi_acc = 0.0, sc_acc = 0.0;
     for (int step = 0; step < nsteps; ++step) {
         LmRows<NR> r;
         const int rowsel = IS_LINE ? ((lane >> (WIDE ? 4 : 3)) & 1) : 0;
-        lm_eval<IS_LINE, NR>(d, rb, S.kc[0][cur.ws], cur.has && S.koff[cur.ws] >= 0, cur.L, cur.meas, cur.wt, cur.has, cur.lvl0, rowsel, true, r);
+        lm_eval<IS_LINE, NR>(d, rb, S.kc[0][cur.ws], cur.has && S.koff[cur.ws] >= 0, cur.L, cur.meas, cur.wt, cur.has, cur.lvl == 0, rowsel, true, r);
         LmStep nxt;
         if (step + 1 < nsteps) lm_load_data<IS_LINE, WIDE>(d, lv, cur_state, lane, ix1, nxt);      // in flight during the rest of the step
         if (step + 2 < nsteps) lm_load_idx<IS_LINE, WIDE>(lv, g, step + 2, wv, lane, ix1);
@@ -874,7 +916,7 @@ DEV void lm_trial_group(const DevBuf& d, const LmView& lv, const int gidx, const
             (void)xa;
         }
         LmRows<NR> rt;
-        lm_eval<IS_LINE, NR>(d, rb, S.kc[1][cur.ws], false, Ltr, cur.meas, cur.wt, cur.has, cur.lvl0, rowsel, false, rt);
+        lm_eval<IS_LINE, NR>(d, rb, S.kc[1][cur.ws], false, Ltr, cur.meas, cur.wt, cur.has, cur.lvl == 0, rowsel, false, rt);
         if (!IS_LINE || rowsel == 0) {
             chi_acc += rt.rho;
             if (rt.act) lv.ob_chi_g[cur.e] = rt.chi;      // (group order: the unit's lanes write neighbouring words; in original order these were 1 M scattered 8-byte stores at configs[4])
