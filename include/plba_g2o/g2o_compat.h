@@ -724,9 +724,7 @@ private:
 inline plba::Cam plba_make_cam(const CamParams& c) {
     plba::Cam cam;
     cam.fx = c.fx; cam.fy = c.fy; cam.cx = c.cx; cam.cy = c.cy;
-    plba::M3 Rbc; for (int i = 0; i < 9; ++i) Rbc.a[i] = c.Rbc[i];
-    cam.Rcb = plba::transpose(Rbc);
-    cam.c0 = plba::mul(cam.Rcb, plba::v3(c.Pbc[0], c.Pbc[1], c.Pbc[2]));
+    plba::cam_set_extrinsics(cam, c.Rbc, c.Pbc);
     return cam;
 }
 

@@ -93,11 +93,13 @@ _quad = None
 
 def new_quad_problem(**opts):
     """The arbiter of ill-conditioned cases: the same source in __float128 (oracle/make_quad.py builds it; real-double entry points
-    orcq_* for upload_window / optimize / gate_outliers / the getters only).  Container only: tests use the fixtures it generated."""
+    orcq_* for upload_window / optimize / gate_outliers / the getters, and orcq_debug_build / orcq_debug_get: the built system in quad,
+    every value rounded to fp64 once on the way out).  Container only: tests use the fixtures it generated."""
     global _quad
     if _quad is None:
         src = os.path.join(_HERE, "plba_oracle.c")
-        if not os.path.exists(QUAD_LIB_PATH) or os.path.getmtime(QUAD_LIB_PATH) < os.path.getmtime(src):
+        gen = os.path.join(_HERE, "make_quad.py")      # (the wrappers live in the generator: a library older than it may lack an entry point)
+        if not os.path.exists(QUAD_LIB_PATH) or os.path.getmtime(QUAD_LIB_PATH) < max(os.path.getmtime(src), os.path.getmtime(gen)):
             subprocess.run([sys.executable, os.path.join(_HERE, "make_quad.py")], check=True)
         _quad = _abi().Lib(QUAD_LIB_PATH, "orcq_", optional=True)
     return _abi().Problem(_quad, **opts)

@@ -1161,9 +1161,7 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
     d.K = K; d.Np = Np; d.Nl = Nl; d.L = L; d.Ep = Ep; d.El = El; d.E = E; d.M = M;
     d.P = p->P; d.Ppad = p->Ppad; d.ld = p->ld; d.npairs = (int)pair_i.size(); d.nent = (int)nent; d.nchunks = (int)ch_meta.size();
     d.cam.fx = w.fx; d.cam.fy = w.fy; d.cam.cx = w.cx; d.cam.cy = w.cy;
-    M3 Rbc; for (int i = 0; i < 9; ++i) Rbc.a[i] = w.Rbc[i];
-    d.cam.Rcb = transpose(Rbc);
-    d.cam.c0 = mul(d.cam.Rcb, v3(w.Pbc[0], w.Pbc[1], w.Pbc[2]));
+    cam_set_extrinsics(d.cam, w.Rbc, w.Pbc);
     d.gw = v3(w.gw[0], w.gw[1], w.gw[2]);
     d.fix_q1 = p->opt.fix_line_position_jacobian;
     d.kf[0] = p->d_kf[0].p; d.kf[1] = p->d_kf[1].p; d.lm[0] = p->d_lm[0].p; d.lm[1] = p->d_lm[1].p;

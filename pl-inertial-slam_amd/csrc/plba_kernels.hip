@@ -459,14 +459,14 @@ DEV EdgeRows load_rows(const DevBuf& d, const double* rec, const double* kc, boo
     if (is_pt) {      // 64-byte point record: camera-frame point, weight, errors
         V3 ua, ub, P;
         point_rows_from_Pc(d.cam, v3(q0.x, q0.y, q0.z), ua, ub, P);
-        rec_row(true, d.fix_q1 != 0, kc, d.cam.Rcb, ua, P, o.va, o.ga);
-        rec_row(true, d.fix_q1 != 0, kc, d.cam.Rcb, ub, P, o.vb, o.gb);
+        rec_row(true, d.fix_q1 != 0, kc, d.cam, ua, P, o.va, o.ga);
+        rec_row(true, d.fix_q1 != 0, kc, d.cam, ub, P, o.vb, o.gb);
         o.w = q0.w; o.e0 = q1.x; o.e1 = q1.y;
         return o;
     }
     const double4 q2 = r4[2], q3 = r4[3];
-    rec_row(false, d.fix_q1 != 0, kc, d.cam.Rcb, v3(q0.x, q0.y, q0.z), v3(q0.w, q1.x, q1.y), o.va, o.ga);
-    rec_row(false, d.fix_q1 != 0, kc, d.cam.Rcb, v3(q1.z, q1.w, q2.x), v3(q2.y, q2.z, q2.w), o.vb, o.gb);
+    rec_row(false, d.fix_q1 != 0, kc, d.cam, v3(q0.x, q0.y, q0.z), v3(q0.w, q1.x, q1.y), o.va, o.ga);
+    rec_row(false, d.fix_q1 != 0, kc, d.cam, v3(q1.z, q1.w, q2.x), v3(q2.y, q2.z, q2.w), o.vb, o.gb);
     o.w = q3.x; o.e0 = q3.y; o.e1 = q3.z;
     return o;
 }
@@ -639,10 +639,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
             point_rows_from_Pc(d.cam, v3(qi[0].x, qi[0].y, qi[0].z), uia, uib, Pia); Pib = Pia;
             point_rows_from_Pc(d.cam, v3(qj[0].x, qj[0].y, qj[0].z), uja, ujb, Pja); Pjb = Pja;
         }
-        rec_row(is_pt, d.fix_q1 != 0, s_kc, d.cam.Rcb, uia, Pia, ri.va, ri.ga);
-        rec_row(is_pt, d.fix_q1 != 0, s_kc, d.cam.Rcb, uib, Pib, ri.vb, ri.gb);
-        rec_row(is_pt, d.fix_q1 != 0, s_kc + KFCAM_STRIDE, d.cam.Rcb, uja, Pja, rj.va, rj.ga);
-        rec_row(is_pt, d.fix_q1 != 0, s_kc + KFCAM_STRIDE, d.cam.Rcb, ujb, Pjb, rj.vb, rj.gb);
+        rec_row(is_pt, d.fix_q1 != 0, s_kc, d.cam, uia, Pia, ri.va, ri.ga);
+        rec_row(is_pt, d.fix_q1 != 0, s_kc, d.cam, uib, Pib, ri.vb, ri.gb);
+        rec_row(is_pt, d.fix_q1 != 0, s_kc + KFCAM_STRIDE, d.cam, uja, Pja, rj.va, rj.ga);
+        rec_row(is_pt, d.fix_q1 != 0, s_kc + KFCAM_STRIDE, d.cam, ujb, Pjb, rj.vb, rj.gb);
         double q00, q01, q10, q11;
         const double ww = wi * wj;
         if (is_pt) {

@@ -8,9 +8,7 @@ using namespace plba;
 static Cam mk_cam(const double* c) {
     Cam cam;
     cam.fx = c[0]; cam.fy = c[1]; cam.cx = c[2]; cam.cy = c[3];
-    M3 Rbc = ld_m3(c + 4);
-    cam.Rcb = transpose(Rbc);
-    cam.c0 = mul(cam.Rcb, v3(c[13], c[14], c[15]));
+    cam_set_extrinsics(cam, c + 4, c + 13);
     return cam;
 }
 extern "C" {
@@ -61,8 +59,8 @@ void hc_rec_edge(const double* camv, const double* nav22, const double* L, const
     if (is_pt) point_edge_rec(cam, kc, v3(L[0], L[1], L[2]), obs[0], obs[1], e2, rec, d, true);
     else line_edge_rec(cam, kc, v3(L[0], L[1], L[2]), v3(L[3], L[4], L[5]), obs[0], obs[1], obs[2], e2, rec, d, true);
     V3 va, vb; double ga[6], gb[6];
-    rec_row(is_pt != 0, fix_q1 != 0, kc, cam.Rcb, v3(rec[0], rec[1], rec[2]), v3(rec[3], rec[4], rec[5]), va, ga);
-    rec_row(is_pt != 0, fix_q1 != 0, kc, cam.Rcb, v3(rec[6], rec[7], rec[8]), v3(rec[9], rec[10], rec[11]), vb, gb);
+    rec_row(is_pt != 0, fix_q1 != 0, kc, cam, v3(rec[0], rec[1], rec[2]), v3(rec[3], rec[4], rec[5]), va, ga);
+    rec_row(is_pt != 0, fix_q1 != 0, kc, cam, v3(rec[6], rec[7], rec[8]), v3(rec[9], rec[10], rec[11]), vb, gb);
     basis_apply(cam.Rcb, ga, Jp12);
     basis_apply(cam.Rcb, gb, Jp12 + 6);
     const double sl = is_pt ? -1.0 : 1.0;
