@@ -93,7 +93,8 @@ typedef struct {
                                    the call site).  0 = always block by block (landmark blocks, then the keyframe block of the reduced
                                    system): identical whenever every discarded direction is a block-local null space.  1 = block by
                                    block when a device-side certificate proves that (no other eigenvalue of Amm at or below the
-                                   threshold, discarded directions uncoupled), the dense path otherwise                       (1) */
+                                   threshold, discarded directions uncoupled) and every kept landmark eigenvalue is resolved by its
+                                   formed block (macheps x largest / kept eigenvalue <= 1e-10), the dense path otherwise      (1) */
     int    lm_fused;            /* the landmark side of an iteration as fused landmark-major passes (plba_lm_dev.h): observations are
                                    evaluated in registers where they are needed — the Schur complement as a rank-k update per group of
                                    landmarks on the matrix cores, back-substitution + trial residuals in one pass — instead of writing a

@@ -261,6 +261,9 @@ struct plba_problem {
     double *pr_x0; /* packed */
     int* pr_x0_off;
     double *pr_J0, *pr_r0, *pr_err;
+    /* the last orc_marginalize's stacked factors, for orc_debug_get("marg_J" / "marg_r" / "marg_layout") */
+    double *mg_J, *mg_r, *mg_lay;
+    size_t mg_nJ, mg_nr, mg_nlay;
     /* robust */
     int rob_on[5];
     double rob_delta[5];
@@ -350,6 +353,7 @@ void orc_destroy(plba_problem* p) {
     free(p->im_err_pvr); free(p->im_err_bias);
     free(p->pr_vid); free(p->pr_size); free(p->pr_idx); free(p->pr_x0); free(p->pr_x0_off);
     free(p->pr_J0); free(p->pr_r0); free(p->pr_err);
+    free(p->mg_J); free(p->mg_r); free(p->mg_lay);
     free(p->off_pvr); free(p->off_bias); free(p->pt_active); free(p->ln_active);
     free(p->pt_xoff); free(p->ln_xoff);
     free(p->Hpp); free(p->bp); free(p->bpg); free(p->Hs); free(p->bs); free(p->x);
@@ -1722,6 +1726,9 @@ int orc_debug_get(plba_problem* p, const char* what, double* out, size_t cap, si
     else if (!strcmp(what, "err_prior")) { src = p->pr_err; cnt = p->pr_nv ? p->pr_n : 0; }
     else if (!strcmp(what, "err_pt")) { src = p->po_err; cnt = (size_t)p->Ep * 2; }
     else if (!strcmp(what, "err_ln")) { src = p->lo_err; cnt = (size_t)p->El * 3; }
+    else if (!strcmp(what, "marg_J")) { src = p->mg_J; cnt = p->mg_nJ; }
+    else if (!strcmp(what, "marg_r")) { src = p->mg_r; cnt = p->mg_nr; }
+    else if (!strcmp(what, "marg_layout")) { src = p->mg_lay; cnt = p->mg_nlay; }
     else if (!strcmp(what, "pose_dim")) { tmp = (double)p->P; src = &tmp; cnt = 1; }
     else if (!strcmp(what, "chi2")) { tmp = p->chi2_last; src = &tmp; cnt = 1; }
     else if (!strcmp(what, "maxdiag")) { tmp = p->maxdiag_last; src = &tmp; cnt = 1; }
@@ -1950,6 +1957,29 @@ int orc_marginalize(plba_problem* p, int first_kf, int max_edges, plba_prior* ou
     int nv_keep = 0;
     for (int i = 0; i < np; ++i) { int a = order[i]; if (!pdrop[a]) { pidx[a] = pos; pos += psz[a]; nv_keep++; } }
     int n = pos - m;
+    /* --- capture for orc_debug_get: the stacked J (R x pos, row-major, this ordering's columns), r, and the layout
+     * [per parameter in column order: id, size, dropped, column offset | m, n, R].  Rows in factor order; the third row of a line
+     * factor, which line_error / line_linearize leave 0, is not a row.  Read only: nothing below depends on it. --- */
+    {
+        int R = 0;
+        for (int fi = 0; fi < nf; ++fi) R += (F[fi].dim == 3) ? 2 : F[fi].dim;
+        free(p->mg_J); free(p->mg_r); free(p->mg_lay);
+        p->mg_J = (double*)xcalloc((size_t)R * pos + 1, 8); p->mg_r = (double*)xcalloc(R + 1, 8); p->mg_lay = (double*)xcalloc(4 * (size_t)np + 3, 8);
+        p->mg_nJ = (size_t)R * pos; p->mg_nr = R; p->mg_nlay = 4 * (size_t)np + 3;
+        int row = 0;
+        for (int fi = 0; fi < nf; ++fi) {
+            factor_t* f = &F[fi];
+            int rows = (f->dim == 3) ? 2 : f->dim;
+            for (int i = 0; i < f->nv; ++i) {
+                int ai; for (ai = 0; ai < np; ++ai) if (pid[ai] == f->vid[i]) break;
+                for (int r = 0; r < rows; ++r) for (int c = 0; c < f->size[i]; ++c) p->mg_J[(size_t)(row + r) * pos + pidx[ai] + c] = f->J[i][(size_t)r * f->size[i] + c];
+            }
+            for (int r = 0; r < rows; ++r) p->mg_r[row + r] = f->r[r];
+            row += rows;
+        }
+        for (int i = 0; i < np; ++i) { int a = order[i]; double* L = p->mg_lay + 4 * i; L[0] = pid[a]; L[1] = psz[a]; L[2] = pdrop[a]; L[3] = pidx[a]; }
+        p->mg_lay[4 * np] = m; p->mg_lay[4 * np + 1] = n; p->mg_lay[4 * np + 2] = R;
+    }
     /* --- A = sum J^T J, b = sum J^T r (ThreadsConstructA, marginalization.cpp:8-36; raw J, no Omega, B-Q4) --- */
     double* A = (double*)xcalloc((size_t)pos * pos, 8);
     double* b = (double*)xcalloc(pos, 8);
@@ -2028,7 +2058,7 @@ int orc_marginalize(plba_problem* p, int first_kf, int max_edges, plba_prior* ou
         if (psz[a] != 9 && psz[a] != 6) { FAIL(p, PLBA_ERR_INVALID, "kept parameter %d is a landmark: only PVR/bias vertices may be kept", pid[a]); }
         out->vid[kv] = pid[a]; out->size[kv] = psz[a]; out->idx[kv] = pidx[a] - m;
         int c = (psz[a] == 9) ? 10 : 6;
-        memcpy(out->x0 + nx, px0[a], 8 * (size_t)c);
+        for (int t = 0; t < c; ++t) out->x0[nx + t] = px0[a][t];      /* (element by element: plba_prior's members are real doubles in every build) */
         nx += c; kv++;
     }
     for (int r = 0; r < n; ++r) { /* J0 = diag(sqrt(S)) V^T (colmajor); r0 = diag(sqrt(S_inv)) V^T b' */

@@ -208,8 +208,9 @@ struct CertBuf {
     int* ndrop;                       // nblk
     unsigned long long* lam_min_bits; // min over blocks of the smallest kept eigenvalue (bits of a positive double order like integers)
     unsigned long long* w2max_bits;   // max over discarded directions of |A[:, block] u|^2
-    int* band;                        // an eigenvalue in (eps, hi]: kept by the block-wise path, counted as discarded by the certificate
+    int* band;                        // an eigenvalue in (eps, hi]: kept by the block-wise path, counted as discarded by the certificate; or a kept one the formed block does not resolve (3)
 };
+constexpr double CERT_RESOLVE = 1e-10;      // certificate, condition (3) below: macheps x (condition of a landmark block's kept part) at most this
 template <int S>
 MDEV void pinv_small(const double* A, int pos, int o, double eps, double* out, bool cert, double hi, const CertBuf cb, int bi) {
     double M[S][S], V[S][S];
@@ -268,10 +269,16 @@ MDEV void pinv_small(const double* A, int pos, int o, double eps, double* out, b
             ph[i * 6 + j] = acc;
         }
     int nd = 0, band = 0;
-    double lmin = 1e300;
+    double lmin = 1e300, wtop = 0.0;
+#pragma unroll
+    for (int k = 0; k < S; ++k) wtop = fmax(wtop, M[k][k]);
 #pragma unroll
     for (int k = 0; k < S; ++k) {
         const double w = M[k][k];
+        // (3) a kept eigenvalue must be resolved by the FORMED block: J_b^T J_b carries macheps |A_bb| of rounding, so 1 / w — and with it
+        // the block's share of A' — carries macheps wtop / w relative.  Beyond CERT_RESOLVE (the 1e-10 A' is held to) the dense path, which
+        // takes the eigenvalues from the columns of J, is the accurate one (a landmark seen once: w / wtop ~ 1e-9, A' off by 1.3e-9).
+        if (w > hi && 1.1102230246251565e-16 * wtop > CERT_RESOLVE * w) band = 1;
         if (w > hi) { lmin = fmin(lmin, w); continue; }
         if (w > eps) band = 1;
 #pragma unroll
@@ -1214,7 +1221,8 @@ __global__ __launch_bounds__(64) void k_dense_schur(double* A, double* b, int po
 //       remaining matrix below hi is the negative inertia of S(hi) = P - hi I - C~_r (Lambda_r - hi)^-1 C~_r^T (Sylvester), so
 //       S(hi) - tau I must be positive definite (Cholesky), tau = max(1e4 w_max, 1e3 macheps trace P): then the tilt of a discarded
 //       direction is <= w_max / tau <= 1e-4 and A' moves by <= 1e-8 relative.
-// Anything else — far landmarks whose depth information falls through the threshold, an eigenvalue in (eps, hi], a keyframe block
+//   (3) every kept landmark eigenvalue is resolved by its formed block: macheps x (largest / kept eigenvalue) <= CERT_RESOLVE (pinv_small).
+// Anything else — far landmarks whose depth information falls through the threshold, a landmark seen once, an eigenvalue in (eps, hi], a keyframe block
 // with a null direction of its own — takes the dense path.
 __global__ __launch_bounds__(64) void k_cert_w(const double* A, int pos, const int* boff, const int* bsize, CertBuf cb) {
     __shared__ double su[36];

@@ -10,7 +10,9 @@ taken as exact inputs, and A = J^T J, the eigen-decomposition of Amm, the thresh
 and r0^T r0 = b'^T A'^+ b' are evaluated with mpmath at 40 digits.
 Cases: the far-landmark windows of tests/test_gpu_parity.py::_far_window (far = 1, 1e2, 1e3, 1e6) and a 12-keyframe window with
 tracks over the whole window (kept block n = 105), all marginalized at their initial estimates (no optimisation in between, so
-the inputs depend on the window generator alone)."""
+the inputs depend on the window generator alone).
+The inputs J and r are the device's own (k_marg_factors is taken as right here); tests/golden/make_marg_quad.py builds the same values
+from the quad-precision oracle's J and r, without the device."""
 import os, sys
 import numpy as np
 import mpmath as mp
@@ -22,28 +24,7 @@ mp.mp.dps = 40
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from marg_cases import CASES, case_window
-
-
-def exact(J, r, m, n, eps):
-    R, pos = J.shape
-    Jm = mp.matrix(J.tolist()); rm = mp.matrix(r.tolist())
-    A = Jm.T * Jm; b = Jm.T * rm
-    E, Q = mp.eigsy(A[0:m, 0:m])
-    W = mp.matrix(m, m)
-    for i in range(m):
-        if E[i] > eps:
-            W[i, i] = 1 / E[i]
-    Ainv = Q * W * Q.T
-    Ar = A[m:pos, m:pos] - A[m:pos, 0:m] * Ainv * A[0:m, m:pos]
-    br = b[m:pos, 0] - A[m:pos, 0:m] * Ainv * b[0:m, 0]
-    E2, Q2 = mp.eigsy(Ar)
-    r0r0 = mp.mpf(0)
-    for i in range(n):
-        if E2[i] > eps:
-            vb = sum(Q2[k, i] * br[k] for k in range(n))
-            r0r0 += vb * vb / E2[i]
-    return (np.array(Ar.tolist(), dtype=float), np.array(br.tolist(), dtype=float).ravel(), float(r0r0),
-            np.array([float(E[i]) for i in range(m)]), np.array([float(E2[i]) for i in range(n)]))
+from marg_mp import exact      # (shared with make_marg_quad.py)
 
 
 if __name__ == "__main__":

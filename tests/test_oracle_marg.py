@@ -41,12 +41,26 @@ def _independent_marg(orc, pkg, w, state, first_kf=0, NUM=50, old_prior=None):
             num += 1
             if num > NUM:
                 break
-    if old_prior is not None:
-        n0 = old_prior["n"]
+    if old_prior is not None:      # the old prior as one factor (mapHandler.cpp:6167-6188): residual = EdgeMarginalization::computeError at the
+        n0 = int(old_prior["n"])   # state (IMU/g2otypes.cpp:1423-1475), columns = those of J0, vertex by vertex
+        J0p = np.asarray(old_prior["J0"]).reshape(n0, n0)
         dx = np.zeros(n0)
-        for v, s, ix, in zip(old_prior["vid"], old_prior["size"], old_prior["idx"]):
-            k = (v // 2) - kf["vid_pvr"][0] // 2
-        raise NotImplementedError
+        blocks, o = [], 0
+        for v, s, ix in zip(old_prior["vid"], old_prior["size"], old_prior["idx"]):
+            v, s, ix = int(v), int(s), int(ix)
+            if s == 9:
+                k = list(kf["vid_pvr"]).index(v)
+                x0 = old_prior["x0"][o:o + 10]; o += 10
+                dx[ix:ix + 3] = state["P"][k] - x0[:3]; dx[ix + 3:ix + 6] = state["V"][k] - x0[3:6]
+                q0, qc = x0[6:10], orc.R_to_quat(orc.quat_to_R(state["q"][k]))      # (x, y, z, w)
+                qi = np.concatenate([-q0[:3], q0[3:]]) / (q0 @ q0)
+                dx[ix + 6:ix + 9] = 2.0 * (qi[3] * qc[:3] + qc[3] * qi[:3] + np.cross(qi[:3], qc[:3]))
+            else:
+                k = list(kf["vid_bias"]).index(v)
+                x0 = old_prior["x0"][o:o + 6]; o += 6
+                dx[ix:ix + 3] = kf["bg"][k] + state["dbg"][k] - x0[:3]; dx[ix + 3:ix + 6] = kf["ba"][k] + state["dba"][k] - x0[3:6]
+            blocks.append((v, J0p[:, ix:ix + s]))
+        factors.append((np.asarray(old_prior["r0"]) + J0p @ dx, blocks))
     ids = sorted({int(pid) for _, bl in factors for pid, _ in bl})
     sizes = {}
     for _, bl in factors:
@@ -153,6 +167,13 @@ def test_prior_edge_error_and_chained_marginalization(orc, pkg):
     assert st.iterations == 3 and np.isfinite(st.chi2_final) and st.chi2_final <= st.chi2_initial
     pr2 = q.marginalize(0, 50)
     assert pr2["n"] > 0 and np.all(np.isfinite(pr2["J0"]))
+    # the second marginalization against the independent restatement, the old prior among its factors, at the first test's tolerances
+    s1 = pkg.protocol.results(q)
+    Ar, br, kept, sizes, m = _independent_marg(orc, pkg, w1, s1, old_prior=pr)
+    assert list(pr2["vid"]) == kept and list(pr2["size"]) == sizes and pr2["m"] == m and pr2["n"] == sum(sizes)
+    sc = np.abs(Ar).max()
+    assert np.allclose(pr2["Ar"], Ar, rtol=1e-6, atol=1e-9 * sc)
+    assert np.allclose(pr2["br"], br, rtol=1e-6, atol=1e-9 * np.abs(br).max())
     # vertices of the dropped keyframe are gone, survivors keep their ids
     assert int(kf["vid_pvr"][0]) not in pr2["vid"] and int(kf["vid_bias"][0]) not in pr2["vid"]
     assert set(int(v) for v in pr["vid"]) - {int(kf["vid_pvr"][0]), int(kf["vid_bias"][0])} <= set(int(v) for v in pr2["vid"])
