@@ -1039,6 +1039,10 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
     std::vector<uint8_t> cov((size_t)K * K, 0);
     for (size_t q = 0; q < pair_i.size(); ++q) { cov[(size_t)pair_i[q] * K + pair_j[q]] = 1; cov[(size_t)pair_j[q] * K + pair_i[q]] = 1; }
     if (p->world > 1) {
+        // The asynchronous table fill build_lm_groups started holds the worker pool (HostPool::start keeps its job lock until finish()).
+        // A rank must not wait in a collective while it holds it: another rank of the SAME process (one thread per problem, plba.h) blocks
+        // in HostPool::start / run on its way to this very collective, and neither moves again.  Join the fill first.
+        HostPool::get().finish();
         std::vector<double> cd((size_t)K * K);
         for (size_t t = 0; t < cd.size(); ++t) cd[t] = cov[t];
         DArr<double> dcov;

@@ -406,28 +406,28 @@ def make_config(idx, scale=1.0, seed=None):
                        seed=(0x5EED0000 + idx) if seed is None else seed)
 
 
-def shard_window(w, rank, world, by="time"):
-    """Landmark shard of a window for rank `rank` of `world` (SURVEY §8e): points and lines are partitioned together with all their
-    observations; keyframes, IMU edges and the prior are replicated (the library adds pose-side edges on rank 0 only).
-    by="time" (round 5): the landmarks are ordered by their FIRST keyframe and cut into `world` equal stretches, so that a rank's
-    landmarks lie in one stretch of the window — its Schur partials touch one stretch of the band of the reduced camera system instead
-    of all of it (with the index-ordered blocks of rounds 1-4 every rank touched every pose-pair block: landmark indices are random in
-    time).  by="index": equal blocks of the landmark index, as before.  Within a shard the landmarks keep their ascending index order.
-    shard["pt_index"] / ["ln_index"]: the window indices of the shard's points / lines."""
+def shard_pick(w, rank, world, by="time"):
+    """(point indices, line indices) of rank `rank`'s shard, ascending: the "pick" half of shard_window"""
     def pick(N, ob_lm, ob_kf):
         if by == "index":
             return np.arange((N * rank) // world, (N * (rank + 1)) // world)
         first = _first_kf(ob_lm.astype(np.int64), ob_kf.astype(np.int64), N)
         order = np.argsort(first, kind="stable")
         return np.sort(order[(N * rank) // world:(N * (rank + 1)) // world])
+    return pick(len(w["points"]), w["po_pt"], w["po_kf"]), pick(len(w["lines"]), w["lo_ln"], w["lo_kf"])
+
+
+def shard_cut(w, pidx, lidx, rank, world, by="explicit"):
+    """The "cut" half of shard_window: the window with the points `pidx` and the lines `lidx` (ascending window indices) and all their
+    observations, renumbered; everything else replicated.  An explicit pair of index lists gives a shard no rule of shard_pick makes
+    (a rank without landmarks, a rank with one kind only)."""
+    pidx, lidx = np.asarray(pidx, np.int64), np.asarray(lidx, np.int64)
     out = dict(w)
-    pidx = pick(len(w["points"]), w["po_pt"], w["po_kf"])
     pos = np.full(len(w["points"]), -1, np.int64); pos[pidx] = np.arange(len(pidx))
     sel = pos[w["po_pt"]] >= 0
     out["points"] = w["points"][pidx]
     out["po_pt"] = pos[w["po_pt"][sel]].astype(np.int32)
     out["po_kf"] = w["po_kf"][sel]; out["po_uv"] = w["po_uv"][sel]; out["po_w"] = w["po_w"][sel]
-    lidx = pick(len(w["lines"]), w["lo_ln"], w["lo_kf"])
     lpos = np.full(len(w["lines"]), -1, np.int64); lpos[lidx] = np.arange(len(lidx))
     lsel = lpos[w["lo_ln"]] >= 0
     out["lines"] = w["lines"][lidx]
@@ -439,6 +439,18 @@ def shard_window(w, rank, world, by="time"):
         out["line_fixed"] = np.asarray(w["line_fixed"])[lidx]
     out["shard"] = dict(rank=rank, world=world, by=by, pt_index=pidx, ln_index=lidx)
     return out
+
+
+def shard_window(w, rank, world, by="time"):
+    """Landmark shard of a window for rank `rank` of `world` (SURVEY §8e): points and lines are partitioned together with all their
+    observations; keyframes, IMU edges and the prior are replicated (the library adds pose-side edges on rank 0 only).
+    by="time" (round 5): the landmarks are ordered by their FIRST keyframe and cut into `world` equal stretches, so that a rank's
+    landmarks lie in one stretch of the window — its Schur partials touch one stretch of the band of the reduced camera system instead
+    of all of it (with the index-ordered blocks of rounds 1-4 every rank touched every pose-pair block: landmark indices are random in
+    time).  by="index": equal blocks of the landmark index, as before.  Within a shard the landmarks keep their ascending index order.
+    shard["pt_index"] / ["ln_index"]: the window indices of the shard's points / lines.  (shard_pick chooses, shard_cut cuts.)"""
+    pidx, lidx = shard_pick(w, rank, world, by)
+    return shard_cut(w, pidx, lidx, rank, world, by)
 
 
 def make_visual_window(K=8, Np=300, Nl=60, n_fixed=2, seed=0x1BA, noise_px=0.5, pose_noise=(0.02, 0.01), lm_noise=0.03, track=6):
