@@ -213,7 +213,15 @@ int plba_set_prior(plba_problem* p, int n, int nv, const int32_t* vid, const int
                    const double* J0_colmajor, const double* r0);  /* nv == 0 clears; mapHandler.cpp:6007-6034 */
 int plba_set_robust(plba_problem* p, plba_edge_kind kind, int enabled, double huber_delta); /* setRobustKernel/setDelta */
 /* setLevel, POINT/LINE only.  New edges are level 0: plba_set_point_obs resets the levels of BOTH kinds (the point count moves
- * the line range), plba_set_line_obs those of the line edges only. */
+ * the line range), plba_set_line_obs those of the line edges only.  The state setters (plba_set_keyframes, plba_set_points,
+ * plba_set_lines) touch neither the levels — those set by plba_set_levels and those plba_gate_outliers left alike — nor the cached
+ * errors of the POINT and LINE edges: after them a level-0 point or line edge still reports the chi2 of the last evaluation pass
+ * (plba_get_edge_chi2, plba_cull_observations), as g2o's edge->chi2() does; new observation arrays start at 0.  The promise covers
+ * these two kinds only: the chi2 of the IMU and prior edges reads 0 after a setter until the next evaluation pass.
+ * A keyframe without any edge — every observation at level 1, no IMU edge, no prior entry — keeps its place in the pose layout
+ * (pose_dim does not depend on the levels; the reference's initializeOptimization(0) would drop the vertex): its rows and columns
+ * of the reduced system hold the damping on the diagonal and exact zeros elsewhere, its part of the step is exactly 0, its estimate
+ * comes back from plba_optimize bit for bit as uploaded, and nothing of it counts as a solver failure. */
 int plba_set_levels(plba_problem* p, plba_edge_kind kind, const uint8_t* level);
 int plba_get_levels(plba_problem* p, plba_edge_kind kind, uint8_t* level);
 

@@ -64,6 +64,7 @@ static void reset_for_reuse(plba_problem* p, const plba_options* opt) {
     p->ob_pos.clear(); p->flow_epoch = 0;
     p->lm_ok = false; p->lm_grouped = false; ++p->state_epoch; p->res_lm_epoch = 0; p->res_lm.clear(); p->lm_hist.clear();
     p->lm_chi_dirty = false; p->back_epoch = 0; p->lm_disable = false; p->lm_spec = false; p->assembled = false;
+    p->chi_E = -1; p->chi_carry = false; p->chi_keep.clear();
     memset(&p->lv, 0, sizeof p->lv);
     p->trace.clear(); p->saved_valid = false;
     memset(p->h_mail, 0, sizeof(Mailbox)); p->mail_seq = 0;
@@ -296,6 +297,7 @@ int plba_set_point_obs(plba_problem* p, int Ep, const int32_t* pt, const int32_t
     if (w) for (int e = 0; e < Ep; ++e) p->win.po_w[e] = (double)(float)w[e];   // const float& invSigma2 (mapHandler.cpp:5340)
     p->win.carry_po = false;
     p->win.level.assign((size_t)p->win.Ep + p->win.El, 0);      // new edges are level 0 (g2o); a re-used handle does not inherit the previous window's
+    p->chi_E = -1; p->chi_carry = false;      // ... and have no cached error
     p->dirty = true;
     return PLBA_OK;
 }
@@ -315,6 +317,7 @@ int plba_set_line_obs(plba_problem* p, int El, const int32_t* ln, const int32_t*
     // to drop them).  plba_set_point_obs still resets both ranges: Ep moves the line range's offset.
     p->win.level.resize((size_t)p->win.Ep + p->win.El);
     std::fill(p->win.level.begin() + std::min((size_t)p->win.Ep, p->win.level.size()), p->win.level.end(), (uint8_t)0);
+    p->chi_E = -1; p->chi_carry = false;
     p->dirty = true;
     return PLBA_OK;
 }
@@ -819,6 +822,7 @@ __global__ void k_prior_scatter(const double* __restrict__ H, int n, int nv, con
 }
 // reads_prior: the caller consumes the prior (plba_optimize, plba_marginalize*, plba_debug_build): a prior that plba_marginalize_to_prior
 // changed on an unchanged window rebuilds it, as plba_set_prior would.  The other callers (results, gating, culling) keep the resident window.
+static void lm_chi_sync(plba_problem* p);
 static int prepare(plba_problem* p, bool reads_prior = false) {
     if (reads_prior && p->prior_changed) p->dirty = true;
     if (!p->dirty) return PLBA_OK;
@@ -867,6 +871,16 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
         return PLBA_ERR_INVALID;      // (p->err holds this rank's finding)
     }
     if ((int)w.level.size() != E) p->win.level.assign(E, 0);
+    // A rebuild that keeps the observation arrays — a state, IMU or prior setter after an evaluation pass — keeps the edges' cached chi2
+    // (include/plba.h: a level-0 edge uses the error cached by the last evaluation pass; the reference's edge->chi2() reads the cached
+    // _error whatever happened to the vertices since).  It is read back from the image about to be rebuilt, whose buffers and views are
+    // untouched so far, and uploaded into the new one below.  A window whose observation arrays were set again never takes this path.
+    if (p->chi_E == E && E > 0 && !p->chi_carry) {
+        lm_chi_sync(p);
+        p->chi_keep.resize((size_t)E);
+        HIPCK(p, plba_d2h(p, p->chi_keep.data(), p->dv.ob_chi2, (size_t)E * 8));
+        p->chi_carry = true;
+    }
     const bool ptime = (p->opt.diag & PLBA_DIAG_TIMING) != 0;
     auto pt0 = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) { if (!ptime) return; auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[prepare] %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - pt0).count()); pt0 = t; };
@@ -1101,7 +1115,8 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
     HIPCK(p, p->d_ob_kf.upload(ob_kf)); HIPCK(p, p->d_ob_slot.upload(ob_slot)); HIPCK(p, p->d_lm_start.upload(lm_start));
     HIPCK(p, p->d_level.upload(w.level)); HIPCK(p, p->d_lm_fixed.upload(p->lm_fixed));
     const size_t nrec = lm_cand ? 0 : ((size_t)Ep + 2 * (size_t)El) * EREC_UNIT;      // the fused passes write no record table (2 x 70 MB at configs[4])
-    HIPCK(p, p->d_ob_chi2.alloc(E)); HIPCK(p, p->d_erec.alloc(nrec + EREC)); HIPCK(p, p->d_erec2.alloc(nrec + EREC)); HIPCK(p, p->d_depth.alloc(E));
+    if (p->chi_carry && (int)p->chi_keep.size() == E) HIPCK(p, p->d_ob_chi2.upload(p->chi_keep)); else HIPCK(p, p->d_ob_chi2.alloc(E));
+    HIPCK(p, p->d_erec.alloc(nrec + EREC)); HIPCK(p, p->d_erec2.alloc(nrec + EREC)); HIPCK(p, p->d_depth.alloc(E));
     HIPCK(p, p->d_lm_active.alloc(L));
     HIPCK(p, p->d_hll.alloc((size_t)L * 12)); HIPCK(p, p->d_bl.alloc((size_t)L * 6)); HIPCK(p, p->d_dinv.alloc((size_t)L * 12));
     HIPCK(p, p->d_tv.alloc((size_t)L * 6)); HIPCK(p, p->d_xl.alloc((size_t)L * 6));
@@ -1731,6 +1746,7 @@ static int prepare(plba_problem* p, bool reads_prior = false) {
     p->cur = 0;
     p->saved_valid = true;
     p->dirty = false;
+    p->chi_E = E; p->chi_carry = false;
     p->prior_changed = false;
     ++p->state_epoch;
     return PLBA_OK;
@@ -2279,6 +2295,11 @@ int plba_gate_outliers(plba_problem* p, double thresh, int* np_out, int* nl_out)
     launch_gate(d, p->cur, thresh, p->stream);
     if (p->lm_ok) launch_lm_level_sync(d, p->lv, p->stream);      // the fused passes read the levels in group order
     HIPCK(p, hipMemcpyAsync(p->h_ctrl, d.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, p->stream));
+    // the gate is the one place where the device changes the levels: the host mirror follows at once, so that a rebuild of the device image
+    // (a state, IMU or prior setter before the next call) uploads the gated levels and not the ones from before the gate
+    const int E = p->win.Ep + p->win.El;
+    if ((int)p->win.level.size() != E) p->win.level.assign(E, 0);
+    if (E) HIPCK(p, hipMemcpyAsync(p->win.level.data(), p->d_level.p, (size_t)E, hipMemcpyDeviceToHost, p->stream));
     HIPCK(p, plba_stream_wait(p, p->stream));
     p->rob.on[PLBA_EDGE_POINT] = 0;    // setRobustKernel(0) on every point / line edge (mapHandler.cpp:6055,6065)
     p->rob.on[PLBA_EDGE_LINE] = 0;
@@ -2529,6 +2550,7 @@ int plba_slide_window(plba_problem* p, const plba_slide* s, int32_t* point_map, 
     // ---- commit: nothing below can fail -----------------------------------------------------------------------------------------------------
     std::swap(p->win, p->win_next);
     p->carry_obs_pending = true;
+    p->chi_E = -1; p->chi_carry = false;      // (all edges are level 0 again and none has been evaluated)
     p->dirty = true;
     if (point_map) memcpy(point_map, pl.pmap.data(), pl.pmap.size() * 4);
     if (line_map) memcpy(line_map, pl.lmap.data(), pl.lmap.size() * 4);

@@ -401,6 +401,11 @@ struct plba_problem {
     std::vector<double> lm_hist;                // diagnostics (plba_debug_get "lm_groups")
     int seg_launch_est = 0;                     // dependent factorisation launches the chain segment-length choice expected (diagnostics)
     bool lm_chi_dirty = false;                  // the fused passes' group-order chi2 cache is newer than DevBuf::ob_chi2
+    // the per-observation chi2 cached by the last evaluation pass belongs to the observation arrays, not to the device image: prepare() carries
+    // it over a rebuild that keeps them (chi_E: the observation count DevBuf::ob_chi2 is valid for, -1 after plba_set_*_obs / a slide / create)
+    int chi_E = -1;
+    bool chi_carry = false;                     // chi_keep holds the cache of the image being rebuilt
+    std::vector<double> chi_keep;
     unsigned back_epoch = 0;                    // k_lm_trial launches since the counters were allocated (DevBuf::back_cnt)
     bool lm_disable = false;                    // prepare() found the structure unfit after the fact and rebuilt for the record-based path
     bool lm_spec = false;                       // the accepted trial's Schur pass + gather are already in the stream (enqueued behind the decision)

@@ -26,6 +26,13 @@ the same sums; 32 for x and chi2_trial, the figure test_solver_accuracy.py takes
 solvers (the device factors a chain-eliminated system, the oracle a dense one);  m = max(64, observations of the busiest keyframe),
 lba_ref.tolerances' count of the longest diagonal sum, and the observation count for chi2 and chi2_trial.  No other constants.
 
+Levels.  A window may carry po_level / lo_level (uint8 per observation) and robust ({kind: (enabled, delta)}); apply() sets them after
+every upload_window, on the build problem and on the trial problem.  Only level-0 observations are rows of the system: they alone count
+towards m, make a landmark free and have their residuals compared (the reference never evaluates a gated edge); a product of gated
+observations only must come out as an exact 0 (it is outside the quad pattern).  Where the levels leave a keyframe without any edge the
+reference drops it from the pose layout and the device does not: pose_map() relates the two, and on the dimensions the reference lacks
+the device must hold exact zeros beside a finite diagonal.
+
 Conditions on a case, asserted by tests/test_build_exact_cpu.py on the references alone:
   (i)   the fixture equals what the quad build computes now;
   (ii)  FACTOR x noise(q) <= 1e-10 for every quantity of the built system and <= 1e-9 for x and for chi2_trial, which is a function of
@@ -58,18 +65,71 @@ def cap(q):
 
 
 # ---- the window's layout --------------------------------------------------------------------------------------------------------------------
+def levels(w):
+    """(point, line) observation levels of a window as bool arrays (True: level 1, gated); a window without the keys has every edge at 0"""
+    out = []
+    for key, n in (("po_level", len(w["po_pt"])), ("lo_level", len(w["lo_ln"]))):
+        out.append(np.zeros(n, bool) if w.get(key) is None else np.asarray(w[key]).astype(bool))
+        assert len(out[-1]) == n, key
+    return out
+
+
+def apply(p, w):
+    """what a case carries besides the arrays upload_window reads — the observation levels and the robust switches — set on a problem
+    right after upload_window(w); a replaced state is in the window's own arrays already"""
+    if w.get("po_level") is not None:
+        p.set_levels(0, np.asarray(w["po_level"], np.uint8))
+    if w.get("lo_level") is not None:
+        p.set_levels(1, np.asarray(w["lo_level"], np.uint8))
+    for kind, (enabled, delta) in sorted((w.get("robust") or {}).items()):
+        p.set_robust(int(kind), bool(enabled), float(delta))
+
+
 def layout(w):
-    """what the norms need of a window: the free (not fixed, observed) landmarks — x carries 3 / 6 entries for each, in order — and the
-    two observation counts m of the floors"""
+    """what the norms need of a window: the free landmarks (not fixed, at least one level-0 observation) — x carries 3 / 6 entries for
+    each, in order —, the level-0 observations (act_pt, act_ln: a gated observation is no row of the system and its residual is not
+    compared) and the two observation counts m of the floors, which count level-0 observations only"""
     Np, Nl = len(w["points"]), len(w["lines"])
     fp = np.zeros(Np, bool) if w.get("point_fixed") is None else np.asarray(w["point_fixed"]).astype(bool)
     fl = np.zeros(Nl, bool) if w.get("line_fixed") is None else np.asarray(w["line_fixed"]).astype(bool)
-    free_pt = ~fp & (np.bincount(w["po_pt"], minlength=Np) > 0)
-    free_ln = ~fl & (np.bincount(w["lo_ln"], minlength=Nl) > 0)
+    gp, gl = levels(w)
+    free_pt = ~fp & (np.bincount(w["po_pt"][~gp], minlength=Np) > 0)
+    free_ln = ~fl & (np.bincount(w["lo_ln"][~gl], minlength=Nl) > 0)
     K = len(w["kf"]["vid_pvr"])
-    per_kf = np.bincount(np.concatenate([w["po_kf"], w["lo_kf"]]).astype(np.int64), minlength=K)
-    n_obs = len(w["po_pt"]) + len(w["lo_ln"])
-    return dict(Np=Np, Nl=Nl, free_pt=free_pt, free_ln=free_ln, n_obs=n_obs, m=max(64, int(per_kf.max(initial=0))), m_chi=max(64, n_obs))
+    per_kf = np.bincount(np.concatenate([w["po_kf"][~gp], w["lo_kf"][~gl]]).astype(np.int64), minlength=K)
+    n_obs = int((~gp).sum() + (~gl).sum())
+    return dict(Np=Np, Nl=Nl, free_pt=free_pt, free_ln=free_ln, act_pt=~gp, act_ln=~gl, n_obs=n_obs, m=max(64, int(per_kf.max(initial=0))), m_chi=max(64, n_obs))
+
+
+def pose_map(w):
+    """the pose layout of the device against the reference's, for a window whose levels leave a keyframe without any edge: the device
+    indexes every non-fixed keyframe whatever the levels (include/plba.h), the reference drops a keyframe that has no level-0
+    observation, no IMU edge and no prior entry (initializeOptimization(0)).  Returns None where the two layouts are the same, else an
+    int array over the device's pose dimensions: the reference's dimension, or -1 for a dimension the reference does not have."""
+    kf = w["kf"]
+    K = len(kf["vid_pvr"])
+    gp, gl = levels(w)
+    act_pvr, act_bias = np.zeros(K, bool), np.zeros(K, bool)
+    act_pvr[w["po_kf"][~gp]] = True; act_pvr[w["lo_kf"][~gl]] = True
+    if w.get("imu") is not None:
+        for k in ("kf_i", "kf_j"):
+            act_pvr[w["imu"][k]] = True; act_bias[w["imu"][k]] = True
+    if w.get("prior") is not None:
+        vid = set(int(v) for v in w["prior"]["vid"])
+        act_pvr |= np.array([int(v) in vid for v in kf["vid_pvr"]]); act_bias |= np.array([int(v) in vid for v in kf["vid_bias"]])
+    out, ref = [], 0
+    for k in range(K):
+        pv, bv = not kf["fixed_pvr"][k], kf["vid_bias"][k] >= 0 and not kf["fixed_bias"][k]
+        parts = [(pv, act_pvr[k], 9), (bv, act_bias[k], 6)]
+        if pv and bv and kf["vid_bias"][k] < kf["vid_pvr"][k]:
+            parts.reverse()
+        for on, act, n in parts:
+            if on and act:
+                out += list(range(ref, ref + n)); ref += n
+            elif on:
+                out += [-1] * n
+    out = np.array(out, np.int64)
+    return None if (out >= 0).all() else out
 
 
 def floor(q, lay):
@@ -150,10 +210,36 @@ def _relmax(da, a):
     return float(np.abs(da).max() / np.abs(a).max()) if a.size and np.abs(a).max() > 0 else (0.0 if not da.size or not np.abs(da).max() else np.inf)
 
 
-def errors(res, ref):
+def _without_dropped(res, pmap, n_free):
+    """`res` in the reference's pose layout (pmap: pose_map()).  On the dimensions the reference does not have the result must hold
+    nothing but a finite diagonal: every off-diagonal entry of Hschur, and bp, bschur and x there, exactly 0."""
+    Pd = int(res["P"])
+    assert len(pmap) == Pd, ("pose_dim", Pd, len(pmap))
+    keep, drop = np.flatnonzero(pmap >= 0), np.flatnonzero(pmap < 0)
+    assert np.array_equal(pmap[keep], np.arange(len(keep)))
+    H = np.asarray(res["Hschur"], np.float64).reshape(Pd, Pd)
+    off = H.copy(); off[drop, drop] = 0.0
+    assert not off[drop].any() and not off[:, drop].any(), "Hschur: an off-diagonal entry in a dimension without any edge"
+    assert np.isfinite(H[drop, drop]).all(), "Hschur: the diagonal of a dimension without any edge is not finite"
+    x = np.asarray(res["x"])
+    assert len(x) == Pd + n_free, ("x", len(x), Pd, n_free)
+    for k, v in (("bp", res["bp"]), ("bschur", res["bschur"]), ("x", x[:Pd])):
+        assert not np.asarray(v)[drop].any(), "%s: not exactly 0 in a dimension without any edge" % k
+    out = dict(res)
+    out["P"] = len(keep)
+    out["Hschur"] = H[np.ix_(keep, keep)].ravel()
+    out["bp"], out["bschur"] = np.asarray(res["bp"])[keep], np.asarray(res["bschur"])[keep]
+    out["x"] = np.concatenate([x[:Pd][keep], x[Pd:]])
+    return out
+
+
+def errors(res, ref, pmap=None):
     """{quantity: distance of `res` (raw arrays of read()) from the reference in the norms above}; quantities the window does not have
-    (no lines, no IMU, no prior) are left out.  Raises AssertionError where a shape differs or Hschur has an entry outside the pattern."""
+    (no lines, no IMU, no prior, no level-0 edge of a kind) are left out.  Raises AssertionError where a shape differs or Hschur has an
+    entry outside the pattern.  pmap: the device's pose layout where it differs from the reference's (pose_map())."""
     a, lay, P = ref.a, ref.lay, ref.P
+    if pmap is not None:
+        res = _without_dropped(res, pmap, len(ref.dl_x))
     assert int(res["P"]) == P, ("pose_dim", res["P"], P)
     out = {}
     for k in RAW:
@@ -161,7 +247,10 @@ def errors(res, ref):
             assert np.asarray(res[k]).shape == a[k].shape, (k, np.asarray(res[k]).shape, a[k].shape)
     for k in ("chi2", "maxdiag"):
         out[k] = abs(float(res[k][0]) - float(a[k][0])) / abs(float(a[k][0]))
-    for k in ("err_pt", "err_ln", "err_pvr", "err_bias", "err_prior"):
+    for k, n, act in (("err_pt", 2, lay["act_pt"]), ("err_ln", 3, lay["act_ln"])):      # the rows of the level-0 observations
+        if act.any():
+            out[k] = _relmax((res[k] - a[k]).reshape(-1, n)[act], a[k].reshape(-1, n)[act])
+    for k in ("err_pvr", "err_bias", "err_prior"):
         if a[k].size:
             out[k] = _relmax(res[k] - a[k], a[k])
     for nm, n in (("pt", 3), ("ln", 6)):
@@ -197,10 +286,11 @@ def tolerances(noise, lay):
     return {q: max(factor(q) * n, floor(q, lay)) for q, n in noise.items()}
 
 
-def hold(res, ref, noise, who, name, trial=None):
-    """every quantity of `res` against the reference under the rule; `trial` = (row, quad row, compare `accepted` too).  Prints quantity,
-    error, noise, tolerance and error / noise before it asserts; returns {quantity: (error, noise, tolerance)}."""
-    err = errors(res, ref)
+def hold(res, ref, noise, who, name, trial=None, pmap=None):
+    """every quantity of `res` against the reference under the rule; `trial` = (row, quad row, compare `accepted` too); pmap: pose_map()
+    for a device result.  Prints quantity, error, noise, tolerance and error / noise before it asserts; returns
+    {quantity: (error, noise, tolerance)}."""
+    err = errors(res, ref, pmap)
     assert set(err) == set(noise) - {"chi2_trial"}, (sorted(err), sorted(noise))
     if trial is not None and "chi2_trial" in noise:      # (no figure: the trial of this case and lambda is not compared, build_exact_cases.TRIAL_DROPPED)
         row, row_q, decided = trial
@@ -223,9 +313,9 @@ def hold(res, ref, noise, who, name, trial=None):
 # ---- the references on the CPU: evaluation, reorderings, noise (generator and CPU test only) -----------------------------------------------
 def evaluate(mk, w, lam):
     """(raw arrays after debug_build(lam, True), first trace row of optimize(1) with user_lambda_init = lam) of the implementation `mk`"""
-    p = mk(); p.upload_window(w); p.debug_build(lam, True)
+    p = mk(); p.upload_window(w); apply(p, w); p.debug_build(lam, True)
     raw = read(p); p.close()
-    p = mk(user_lambda_init=lam); p.upload_window(w); p.optimize(1)
+    p = mk(user_lambda_init=lam); p.upload_window(w); apply(p, w); p.optimize(1)
     row = first_trial(p); p.close()
     return raw, row
 
@@ -235,7 +325,8 @@ def reorder(w, seed):
     undoes it: (window, landmark permutations (points, lines), observation orders (points, lines))"""
     rng = np.random.default_rng(seed)
     w2, inv, orders = dict(w), [], []
-    for lm, idx, keys, fx in (("points", "po_pt", ("po_pt", "po_kf", "po_uv", "po_w"), "point_fixed"), ("lines", "lo_ln", ("lo_ln", "lo_kf", "lo_l", "lo_w"), "line_fixed")):
+    for lm, idx, keys, fx in (("points", "po_pt", ("po_pt", "po_kf", "po_uv", "po_w", "po_level"), "point_fixed"),
+                              ("lines", "lo_ln", ("lo_ln", "lo_kf", "lo_l", "lo_w", "lo_level"), "line_fixed")):
         n = len(w[lm]); perm = rng.permutation(n); iv = np.empty(n, np.int64); iv[perm] = np.arange(n)      # new landmark j is old perm[j]
         w2[lm] = w[lm][perm]
         if w.get(fx) is not None:
@@ -243,7 +334,8 @@ def reorder(w, seed):
         new_idx = iv[w[idx]] if len(w[idx]) else np.zeros(0, np.int64)
         order = np.lexsort((rng.random(len(new_idx)), new_idx))                                            # new observation e is old order[e]
         for k in keys:
-            w2[k] = (new_idx.astype(w[idx].dtype) if k == idx else w[k])[order]
+            if w.get(k) is not None:      # (the levels are there only where a case sets them)
+                w2[k] = (new_idx.astype(w[idx].dtype) if k == idx else np.asarray(w[k]))[order]
         inv.append(iv); orders.append(order)
     return w2, inv, orders
 
@@ -302,12 +394,17 @@ def generate(name, W, orc, prior=None):
         from importlib import import_module
         protocol = import_module(W.__name__.rsplit(".", 1)[0] + ".protocol")
         o = orc.new_problem(); o.upload_window(case["make"](W, None)); protocol.local_ba(o); prior = _prior(o.marginalize(0, 50)); o.close()
+    if name in BC.NEEDS_STATE and prior is None:
+        prior = BC.stage1_state(orc, BC.CASES[BC.NEEDS_STATE[name]]["make"](W, None))
     w = case["make"](W, prior)
     out = {"sha": np.array(BC.window_sha(w))}
     if name in BC.NEEDS_PRIOR:
         for k in ("n", "vid", "size", "idx", "x0", "J0", "r0"):
             out["prior/" + k] = np.asarray(prior[k])
-    o = orc.new_quad_problem(); o.upload_window(w); o.debug_build(5.0, False); maxdiag = float(o.debug_get("maxdiag")[0]); o.close()
+    if name in BC.NEEDS_STATE:
+        for k in BC.STATE_KEYS:
+            out["state/" + k] = np.asarray(prior[k])
+    o = orc.new_quad_problem(); o.upload_window(w); apply(o, w); o.debug_build(5.0, False); maxdiag = float(o.debug_get("maxdiag")[0]); o.close()
     lams = BC.lambdas_of(name, maxdiag)
     out["lams"] = np.array([v for _, v in lams])
     for i, (label, lam) in enumerate(lams):
@@ -341,4 +438,7 @@ def _prior(pr):
 
 
 def prior_of(fx):
+    """what a fixture carries for its case's make(): the prior of prior13, the state and levels of a stage2 case, None elsewhere"""
+    if "state/P" in fx:
+        return {k: fx["state/" + k] for k in BC.STATE_KEYS}
     return _prior({k: fx["prior/" + k] for k in ("n", "vid", "size", "idx", "x0", "J0", "r0")}) if "prior/n" in fx else None

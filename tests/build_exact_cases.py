@@ -11,8 +11,24 @@ by a GPU test under the 1e-9 max-norm comparison:
   prior13                          tests/test_group_tiling.py wide13_s5 with the marginalization prior of its own first BA: err_prior
   fixed8                           std_s3 with a fixed middle keyframe and fixed points and lines past the first step of their groups
 
+The gated cases put the same windows into the state two thirds of a local BA's iterations run in — some observations at
+level 1, the point and line Huber kernels off — and reach what only the levels reach:
+  gated_mixed, levels_robust_on    the generator's planted outliers gated, one point and one line without any level-0 observation (x
+                                   shrinks), one point and one line left with one observation, the first observation — the
+                                   first-keyframe bucket's anchor — of five landmarks gated; robust off, and on (wr = 0 apart from rho')
+  gated_short2                     one of the two observations of every fourth point: pairs whose only product vanishes
+  gated_steps3                     gated observations in the second and third step of their groups, one group's whole second step
+  gated_k16                        wide groups with holes: keyframe 5 of each third landmark, one landmark left with one observation
+  lines_all_gated                  a kind without an active edge
+  noimu_lostkf                     every observation of keyframe 3: the reference drops the keyframe from its pose index, the device
+                                   keeps it (include/plba.h); build_exact.pose_map relates the two layouts
+  behind                           level 0 everywhere; three points, the first end of a line, the second of another and both of a third behind a camera
+  stage2_mixed, stage2_cross9      state and levels of the quad oracle's own optimize(5) + gate_outliers(5.991), carried by the fixture
+
 A case is dict(make, opts, wide, lambdas):
-  make(window_module, prior) -> the window (`prior`: the dict the fixture carries for prior13, None elsewhere);
+  make(window_module, carried) -> the window (`carried`: what the fixture carries for the case — the prior of prior13, the state and
+  levels of the stage2 cases —, None elsewhere).  Besides what upload_window reads a window may hold po_level / lo_level (uint8 per
+  observation) and robust ({kind: (enabled, delta)}); build_exact.apply sets them after every upload, window_sha covers them;
   opts: the options the device problem takes besides lm_fused;   wide: wide groups are meant to run;
   lambdas: "init" stands for 1e-5 x maxdiag (what the protocol starts from), 5.0 is what every 1e-9 test uses, 0.05 about where
   fifteen accepted steps end.  Nothing lower: at 1e-4 the Schur complement cancels and the reference's own noise reaches 1e-9.
@@ -64,6 +80,184 @@ def _case(make, lambdas=ALL, wide=False, **opts):
     return dict(make=make, opts=opts, wide=wide, lambdas=lambdas)
 
 
+LMF_W, LMF_UNITS = 8, 32      # a standard group's keyframe window and the units of one workgroup step (a point is 1 unit, a line 2)
+
+
+def _group_steps(w, steps, kind):
+    """[(landmark indices in group order, step of each)] of the standard groups of a window whose groups the host cuts by count alone
+    (tests/test_group_tiling.py _groups): landmarks in (first keyframe, last keyframe, index) order, cut every 32 * steps points /
+    16 * steps lines"""
+    lm, kf, n = (w["lo_ln"], w["lo_kf"], len(w["lines"])) if kind else (w["po_pt"], w["po_kf"], len(w["points"]))
+    cnt = np.bincount(lm, minlength=n)
+    assert cnt.max() <= LMF_W
+    kmin = np.full(n, 1 << 30); np.minimum.at(kmin, lm, kf)
+    kmax = np.full(n, -1); np.maximum.at(kmax, lm, kf)
+    idx = np.flatnonzero(cnt > 0)
+    idx = idx[np.lexsort((idx, kmax[idx], kmin[idx]))]
+    cap = (16 if kind else 32) * steps
+    return [(idx[a:a + cap], (np.arange(len(idx[a:a + cap])) * (2 if kind else 1)) // LMF_UNITS) for a in range(0, len(idx), cap)]
+
+
+def _obs_of(w, kind, i):
+    return np.flatnonzero((w["lo_ln"] if kind else w["po_pt"]) == i)
+
+
+def _robust_off(w):
+    w["robust"] = {0: (0, w["huber"][0]), 1: (0, w["huber"][1])}      # what gate_outliers leaves: setRobustKernel(0) on every point and line edge
+    return w
+
+
+def _mixed_levels(W, robust_on):
+    w = CASES["mixed"]["make"](W, None)
+    lv = [w["truth"]["point_outlier"].astype(np.uint8), w["truth"]["line_outlier"].astype(np.uint8)]
+    assert (int(lv[0].sum()), len(lv[0]), int(lv[1].sum()), len(lv[1])) == (9, 195, 3, 43)
+    for kind in (0, 1):
+        cnt = np.bincount(w["lo_ln"] if kind else w["po_pt"])
+        long = [int(i) for i in np.flatnonzero(cnt >= 3)]      # (tracks of three and more: what is gated below leaves the others of the landmark)
+        lv[kind][_obs_of(w, kind, long[0])] = 1                # every observation of one landmark
+        lv[kind][_obs_of(w, kind, long[1])[:-1]] = 1           # all but the last of another
+        for i in (long[2:6] if kind == 0 else long[2:3]):      # the first observation of four points and one line
+            lv[kind][_obs_of(w, kind, i)[0]] = 1
+    w["po_level"], w["lo_level"] = lv
+    return w if robust_on else _robust_off(w)
+
+
+def _gated_short2(W, carried):
+    w = CASES["short2"]["make"](W, None)
+    lv = np.zeros(len(w["po_pt"]), np.uint8)
+    for n, i in enumerate(range(0, len(w["points"]), 4)):      # alternately the first and the second of the two
+        ob = _obs_of(w, 0, i); assert len(ob) == 2
+        lv[ob[n % 2]] = 1
+    w["po_level"], w["lo_level"] = lv, np.zeros(0, np.uint8)
+    return _robust_off(w)
+
+
+def _gated_steps3(W, carried):
+    w = CASES["steps3"]["make"](W, None)
+    lv = [np.zeros(len(w["po_pt"]), np.uint8), np.zeros(len(w["lo_ln"]), np.uint8)]
+    for kind in (0, 1):
+        groups = _group_steps(w, 3, kind)
+        assert max(int(st.max()) for _, st in groups) == 2
+        for g, (ch, st) in enumerate(groups):
+            for n, i in enumerate(ch[st >= 1]):      # in the second and third step: one observation of every third landmark, first, middle, last in turn
+                if n % 3 == 0:
+                    ob = _obs_of(w, kind, i)
+                    lv[kind][ob[(0, len(ob) // 2, len(ob) - 1)[(n // 3) % 3]]] = 1
+            if g == 0 and kind == 0:                 # and the whole second step of the first point group: 32 points without a level-0 observation
+                assert (st == 1).sum() == 32
+                for i in ch[st == 1]:
+                    lv[kind][_obs_of(w, kind, i)] = 1
+    w["po_level"], w["lo_level"] = lv
+    return _robust_off(w)
+
+
+def _gated_k16(W, carried):
+    w = CASES["k16_all"]["make"](W, None)
+    lv = [(w["po_kf"] == 5) & (w["po_pt"] % 3 == 0), (w["lo_kf"] == 5) & (w["lo_ln"] % 3 == 0)]
+    lv = [a.astype(np.uint8) for a in lv]
+    assert lv[0].sum() > 0 and lv[1].sum() > 0
+    cnt = np.bincount(w["po_pt"])
+    lone = int(np.flatnonzero((cnt > LMF_W) & (np.arange(len(cnt)) % 3 != 0))[0])
+    lv[0][_obs_of(w, 0, lone)[1:]] = 1               # one point of a wide group (more than 8 observations) left with its first observation alone
+    w["po_level"], w["lo_level"] = lv
+    return _robust_off(w)
+
+
+def _lines_all_gated(W, carried):
+    w = CASES["mixed"]["make"](W, None)
+    w["po_level"], w["lo_level"] = np.zeros(len(w["po_pt"]), np.uint8), np.ones(len(w["lo_ln"]), np.uint8)
+    return w
+
+
+def _noimu_lostkf(W, carried):
+    w = CASES["noimu7"]["make"](W, None)
+    w["po_level"], w["lo_level"] = (w["po_kf"] == 3).astype(np.uint8), (w["lo_kf"] == 3).astype(np.uint8)
+    assert w["po_level"].any() and w["lo_level"].any()
+    return w
+
+
+def camera_of(w, k):
+    """(R, C) of keyframe k's camera at the window's estimate: Pc = R (Pw - C) (Pc = Rcb Rwb^T (Pw - Pwb) - Rcb Pbc)"""
+    x, y, z, s = w["kf"]["q"][k]
+    Rwb = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * s), 2 * (x * z + y * s)],
+                    [2 * (x * y + z * s), 1 - 2 * (x * x + z * z), 2 * (y * z - x * s)],
+                    [2 * (x * z - y * s), 2 * (y * z + x * s), 1 - 2 * (x * x + y * y)]])
+    Rbc, Pbc = np.asarray(w["cam"]["Rbc"]), np.asarray(w["cam"]["Pbc"])
+    return Rbc.T @ Rwb.T, w["kf"]["P"][k] + Rwb @ Pbc
+
+
+def project(w, k, X):
+    """(u, v, depth) of the world point X in keyframe k"""
+    R, C = camera_of(w, k)
+    Pc = R @ (np.asarray(X) - C)
+    c = w["cam"]
+    return c["fx"] * Pc[0] / Pc[2] + c["cx"], c["fy"] * Pc[1] / Pc[2] + c["cy"], Pc[2]
+
+
+BEHIND_POINTS, BEHIND_LINE_FIRST_END, BEHIND_LINE_SECOND_END, BEHIND_LINE_BOTH = (4, 17, 33), 6, 3, 9
+
+
+def _behind(W, carried):
+    """mixed with three points, the first end of one line, the second end of another and both ends of another moved along their viewing rays to 0.3 m behind the last
+    keyframe that observes them; every observation of those landmarks becomes the projection of the moved estimate plus pixel noise of
+    the generator's sigma (1 px), so that these edges are bad by depth and not by chi2"""
+    w = dict(CASES["mixed"]["make"](W, None))
+    for k in ("points", "lines", "po_uv", "lo_l"):
+        w[k] = w[k].copy()
+    rng = W.Rng(0xBE41D)
+
+    def moved(X, k):
+        R, C = camera_of(w, k)
+        Pc = R @ (X - C)
+        assert Pc[2] > 0
+        return C + R.T @ (Pc * (-0.3 / Pc[2]))
+    for i in BEHIND_POINTS:
+        ob = _obs_of(w, 0, i)
+        w["points"][i] = moved(w["points"][i], w["po_kf"][ob[-1]])
+        for e in ob:
+            u, v, _ = project(w, w["po_kf"][e], w["points"][i])
+            w["po_uv"][e] = np.array([u, v]) + rng.normal(2)
+    # (one line with the first end alone behind, one with the second alone: a kernel that tests either end only misses one of them)
+    for i, ends in ((BEHIND_LINE_FIRST_END, (0,)), (BEHIND_LINE_SECOND_END, (3,)), (BEHIND_LINE_BOTH, (0, 3))):
+        ob = _obs_of(w, 1, i)
+        for o in ends:
+            w["lines"][i, o:o + 3] = moved(w["lines"][i, o:o + 3], w["lo_kf"][ob[-1]])
+        for e in ob:
+            a, b = (np.array(project(w, w["lo_kf"][e], w["lines"][i, o:o + 3])[:2]) + rng.normal(2) for o in (0, 3))
+            l = np.cross(np.append(a, 1.0), np.append(b, 1.0))
+            w["lo_l"][e] = l / np.hypot(l[0], l[1])
+    return w
+
+
+STATE_KEYS = ("P", "V", "q", "dbg", "dba", "points", "lines", "po_level", "lo_level")
+
+
+def stage1_state(orc, w):
+    """what the stage2 cases carry: keyframes, points, lines (rounded to fp64 on the way out) and levels of the quad oracle's own
+    optimize(5) + gate_outliers(5.991) on `w` — the system stage 2 of a local BA really starts from, through no fp64 optimiser path"""
+    o = orc.new_quad_problem(); o.upload_window(w); o.optimize(5); o.gate_outliers(5.991)
+    st = dict(o.get_keyframes()); st["points"], st["lines"] = o.get_points(), o.get_lines()
+    st["po_level"], st["lo_level"] = o.get_levels(0), o.get_levels(1)
+    o.close()
+    return st
+
+
+def with_state(w, st, levels=True):
+    """the window at a carried state (stage1_state); with its levels and the robust kernels off, as gate_outliers leaves them"""
+    w = dict(w); w["kf"] = dict(w["kf"])
+    for k in ("P", "V", "q", "dbg", "dba"):
+        w["kf"][k] = np.asarray(st[k], np.float64).copy()
+    w["points"], w["lines"] = np.asarray(st["points"], np.float64).copy(), np.asarray(st["lines"], np.float64).copy()
+    if levels:
+        w["po_level"], w["lo_level"] = np.asarray(st["po_level"], np.uint8), np.asarray(st["lo_level"], np.uint8)
+        _robust_off(w)
+    return w
+
+
+def _stage2(base):
+    return lambda W, carried: with_state(CASES[base]["make"](W, None), carried)
+
+
 CASES = {
     "short2": _case(lambda W, pr: W.make_window(6, 40, 0, imu=True, seed=0xBA1A, track=(2, 2))),
     "mixed": _case(lambda W, pr: W.make_window(10, 60, 12, imu=True, seed=0xBA1B, track=(2, 8))),
@@ -78,18 +272,46 @@ CASES = {
     "prior13": _case(_prior13, ONE, wide=True, lm_group_steps=5),
     "fixed8": _case(_fixed8, lm_group_steps=3),
 }
+OLD = tuple(CASES)      # the windows as uploaded: every edge at level 0, Huber on
+CASES.update({
+    "gated_mixed": _case(lambda W, c: _mixed_levels(W, False)),
+    "levels_robust_on": _case(lambda W, c: _mixed_levels(W, True)),
+    "gated_short2": _case(_gated_short2),
+    "gated_steps3": _case(_gated_steps3, lm_group_steps=3),
+    "gated_k16": _case(_gated_k16, ONE, wide=True),
+    "lines_all_gated": _case(_lines_all_gated),
+    "noimu_lostkf": _case(_noimu_lostkf),
+    "behind": _case(_behind),
+    "stage2_mixed": _case(_stage2("mixed")),
+    "stage2_cross9": _case(_stage2("cross9")),
+})
 NEEDS_PRIOR = ("prior13",)      # the prior is data the fixture carries (the reference's marginalization of the window's own first BA)
+NEEDS_STATE = {"stage2_mixed": "mixed", "stage2_cross9": "cross9"}      # state and levels the fixture carries (stage1_state of the named window)
 
 # What condition (ii) of tests/build_exact.py — FACTOR x the reference's own noise within the cap — removed, judged on the references alone
 # (tests/golden/make_build_exact.py prints every noise figure and names what is over its cap), in units of u = 2^-53:
 #   mixed 0.05         x_pose 916 581 u (32 x = 3.3e-9), x_lm 311 582 u, chi2_trial 1 009 151 u      (Hschur 46 558 u: 8 x = 4.1e-11, within)
 #   lines_only 0.05    x_pose 13 284 250 u (32 x = 4.7e-8), x_lm 1 738 550 u, chi2_trial 8 659 759 u
-# These two lose lambda = 0.05 altogether.  On two more only the first trial's chi2 is over its cap while the system and x are within:
+# These two lose lambda = 0.05 altogether.  (tests/test_build_exact_cpu.py recomputes every dropped pair's noise and asserts that it is over its cap.)  On two more only the first trial's chi2 is over its cap while the system and x are within:
 #   points_only 0.05   chi2_trial 1 389 847 u (32 x = 4.9e-9)
 #   noimu7 0.05        chi2_trial 5 336 431 u (32 x = 1.9e-8)
 # there the built system and x are held and the trial is not compared.
-DROPPED = {("mixed", 0.05), ("lines_only", 0.05)}
-TRIAL_DROPPED = {("points_only", 0.05), ("noimu7", 0.05)}
+# The gated cases (caps: 112 590 u on a quantity of the system, 281 475 u on x and chi2_trial), each judged before any device ran:
+#   gated_mixed 0.05       x_pose 2 097 882 u, x_lm 1 790 251 u, chi2_trial 9 722 725 u      (Hschur 34 300 u, within)
+#   gated_short2 0.05      x_pose 758 434 u, x_lm 296 635 u, chi2_trial 382 507 u
+#   gated_steps3 0.05      x_pose 3 222 239 u, x_lm 548 301 u, chi2_trial 1 928 990 u
+#   noimu_lostkf 0.05      x_pose 387 304 u                                                 (chi2_trial 115 797 u, within)
+#   behind 5               Hschur 432 636 u, x_pose 890 546 848 u, x_lm 342 888 422 u, chi2_trial 119 139 685 u
+#   behind 0.05            Hschur 557 319 u, x_pose 2 421 281 518 u, x_lm 1 111 928 241 u, chi2_trial 2 236 393 559 u
+#   stage2_mixed 0.05      x_pose 1 072 270 u, chi2_trial 417 188 u
+#   stage2_cross9 0.05     x_pose 3 069 271 u, x_lm 1 266 891 u, chi2_trial 5 358 475 u
+# (`behind` keeps the protocol's own first lambda only: a landmark 0.3 m from a camera has Jacobians a hundred times those of the rest of
+# the window and the solve loses the digits; its built system — the rows with z < 0 — is held there.)  The trial alone:
+#   levels_robust_on 0.05  chi2_trial 559 790 u                                             (x_pose 207 137 u, x_lm 209 660 u, within)
+DROPPED = {("mixed", 0.05), ("lines_only", 0.05),
+           ("gated_mixed", 0.05), ("gated_short2", 0.05), ("gated_steps3", 0.05), ("noimu_lostkf", 0.05), ("behind", 5.0), ("behind", 0.05),
+           ("stage2_mixed", 0.05), ("stage2_cross9", 0.05)}
+TRIAL_DROPPED = {("points_only", 0.05), ("noimu7", 0.05), ("levels_robust_on", 0.05)}
 
 
 def lambdas_of(name, maxdiag):

@@ -1,6 +1,8 @@
 """Writes tests/golden/build_exact_<case>.npz for the cases of tests/build_exact_cases.py: the built system of the quad-precision oracle
 (oracle/make_quad.py: orcq_debug_build / orcq_debug_get), the fp64 oracle's noise against it and the first trial of optimize(1), per
-lambda; tests/build_exact.py says what the figures are and how they are used.  CPU only, seconds per case.
+lambda; tests/build_exact.py says what the figures are and how they are used.  A case that carries levels, robust switches or a
+replaced state (the gated cases) is built with them: build_exact.apply after every upload; the stage2 cases store the state and levels
+of the quad oracle's own optimize(5) + gate_outliers.  CPU only, seconds per case.
 
     python tests/golden/make_build_exact.py [case ...]
 

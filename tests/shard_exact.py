@@ -269,7 +269,7 @@ EVERY_RANK_HAS_OBSERVATIONS = {"empty_rank": False, "one_bucket": True, "lines_o
 # global: every rank of such a window takes the record-based passes, whatever lm_fused asks for.  The tests assert exactly that.)
 
 # (case, world, lambda label, edge cut or None)
-RUNS = [(name, 3, 5.0, None) for name in BC.CASES]
+RUNS = [(name, 3, 5.0, None) for name in BC.OLD]      # the twelve windows as uploaded (the gated cases of DESIGN.md 9l carry levels, which a shard cut does not)
 for _W in (2, 8):
     RUNS += [("k6", _W, "init", None), ("k6", _W, 5.0, None), ("k6", _W, 0.05, None)]
     RUNS += [(name, _W, 5.0, None) for name in ("prior13", "fixed8", "noimu7", "k14_lines")]
