@@ -733,6 +733,82 @@ int  plba_track_pose(plba_problem* p, const plba_track_options* opt, int B,
                      double fx, double fy, double cx, double cy, const double* T0_16,
                      uint8_t* pt_inlier, uint8_t* ln_inlier, plba_track_result* out);
 
+/* ---- visual-inertial tracking: batched motion-only optimisation of two states ------------------------------
+ * The 15-DoF family of IMU/g2otypes.h:411-695 (VertexNavState, EdgeNavState, EdgeNavStatePointXYZOnlyPose, EdgeNavStatePrior), which the
+ * reference defines and never instantiates, as ONE graph per problem, B problems in ONE launch, one wave per problem and the whole
+ * protocol inside the launch.  The graph:
+ *   two VertexNavState in the 22-double layout of NavState::raw() (P, V, q_xyzw, bg, ba, dbg, dba): i the anchor (vertex id 0), j the new
+ *   frame (id 1); the update is IncSmall (P += R dP, V += dV, q = q Exp(dPhi) renormalised, dbg += ., dba += .).  anchor_free[b] = 0 (or
+ *   anchor_free = NULL) fixes i: 15 unknowns.  anchor_free[b] = 1 frees i and attaches an EdgeNavStatePrior(prior_state22, prior_info225)
+ *   to it: 30 unknowns, ordered [i | j];
+ *   one EdgeNavState(i, j): preint142 in the layout of plba_set_imu_edges, information blockdiag(info_pvr81, info_bias36), gravity gw3
+ *   (one for the call), an optional Huber kernel huber_imu on its 15-dimensional chi2 (0: none);
+ *   pose-only point edges on j (Pw3, uv2, inv_sigma2; EdgeNavStatePointXYZOnlyPose) and pose-only line edges on j (sPeP6, l3, inv_sigma2;
+ *   the two rows of EdgeNavStateLine with the line held, its Jacobian the TRUE derivative under IncSmall, i.e. that of
+ *   fix_line_position_jacobian = 1: SURVEY B-Q1 is a defect of the BA's edge and is not carried over), CSR over the problems as in
+ *   plba_track_pose; one camera (fx fy cx cy Rbc9 Pbc3) for the call.  A problem without any visual edge is legal.
+ * The protocol: `rounds` rounds.  A round is g2o's Levenberg loop as SparseOptimizer::optimizeHost of include/plba_g2o/g2o_compat.h states
+ * it, for `iters` iterations: lambda = tau max|H_ii| (or user_lambda_init > 0) at the START OF EVERY ROUND, as a new optimize() call
+ * would; a trial solves (H + lambda I) x = b by LL^T, a pivot that is not > 0 a solver failure (the trial is rejected);
+ * scale = 1e-3 + sum x (lambda x + b), rho = (chi - chi') / scale; accepted (rho > 0, chi' finite): lambda *= max(1/3, min(2/3,
+ * 1 - (2 rho - 1)^3)), nu = 2; rejected: lambda *= nu, nu *= 2; at most max_trials trials while rho < 0.  A round stops
+ * (stop_reason) on 1: qmax == max_trials, 2: rho == 0, 3: a non-finite lambda; 0: it ran its iterations.  The visual edges carry Huber
+ * kernels huber_pt / huber_ln while round < robust_rounds and none afterwards.  After EVERY round the gate: for every visual edge,
+ * active or not, chi2 = inv_sigma2 e^T e at the estimate; mask 0 when chi2 > chi2_pt / chi2_ln or the depth (of either end point) is not
+ * positive, else mask 1: edges are re-admitted as well as dropped.  After the last round the active edges are linearised once at the
+ * final estimate with the last round's kernel setting and no damping: H900, 30 x 30 row-major in [i | j] order, exactly symmetric, the
+ * rows and columns of a fixed i zero.  S = H_jj - H_ji H_ii^-1 H_ij (H_jj when i is fixed) and next_prior_info225 = J^-T S J^-1 with
+ * J = blockdiag(-R_j, -I, I, -I, -I), the Jacobian of an EdgeNavStatePrior at zero error at j: such an edge with measurement state_j22
+ * and this information has S as its Hessian, which is how frame n's result becomes frame n + 1's prior.  A pivot of H_ii or of S that is
+ * not > 0: PLBA_VITRACK_SINGULAR, next_prior_info225 = 0, the states and H900 still reported.  chi2_initial is the (robustified) chi2 of
+ * the active edges at entry under round 0's kernels, chi2_final that of the final linearisation.  A non-finite chi2 at the head of an
+ * iteration or at the final linearisation ends the run: PLBA_VITRACK_NONFINITE (stop_reason 4), H900 = 0, next_prior_info225 = 0.
+ * rounds = 0 or iters = 0 return the states bit for bit and still report H900; a fixed i always comes back bit for bit.
+ * pt_inlier / ln_inlier: in/out masks as in plba_track_pose, NULL on input = all active.  Quaternions are taken as plba_set_keyframes
+ * takes them: stored as given, normalised where the reference's accessors normalise.
+ * Refused with PLBA_ERR_INVALID and every output untouched: the refusals of plba_track_pose about CSR arrays, NULLs and non-finite
+ * input; a negative inv_sigma2; rounds outside [0, 8]; a negative iters, max_trials or robust_rounds; a non-finite option;
+ * anchor_free[b] = 1 without the prior arrays.  `p` supplies the device, the stream and the error text; the uploaded window, prior,
+ * trace and saved state are neither read nor written.  One staged copy up, one back, one blocking wait
+ * (plba_debug_get("host_waits")).  A problem's result does not depend on B or on its neighbours; two calls give the same bits.
+ * include/plba_g2o/track_inertial.h is the same protocol on the host for a caller without a device. */
+#define PLBA_VITRACK_OK 0
+#define PLBA_VITRACK_NONFINITE 2  /* a non-finite chi2 ended the run                              */
+#define PLBA_VITRACK_SINGULAR 3   /* H_ii or S has a pivot that is not > 0: no next prior         */
+typedef struct plba_vitrack_options {
+    int    rounds;            /* optimisation rounds, each followed by the gate, 0 .. 8   (4)     */
+    int    iters;             /* Levenberg iterations per round                           (10)    */
+    int    max_trials;        /* g2o's maxTrialsAfterFailure                              (10)    */
+    int    robust_rounds;     /* rounds with Huber kernels on the visual edges            (2)     */
+    double tau;               /* lambda = tau max|H_ii|                                   (1e-5)  */
+    double user_lambda_init;  /* > 0: the initial lambda of every round                   (0)     */
+    double huber_pt, huber_ln;/* (double)(float)sqrt(5.991), src/mapHandler.cpp:5896,5956         */
+    double huber_imu;         /* Huber delta of the IMU edge, 0 = no kernel               (0)     */
+    double chi2_pt, chi2_ln;  /* the gate's thresholds, src/mapHandler.cpp:6051           (5.991) */
+} plba_vitrack_options;
+typedef struct plba_vitrack_result {
+    double  state_i22[22];    /* the input bits when i is fixed                                  */
+    double  state_j22[22];
+    double  H900[900];        /* the final linearisation, [i | j], row-major, symmetric          */
+    double  next_prior_info225[225];   /* J^-T S J^-1: the information of an EdgeNavStatePrior on j */
+    double  chi2_initial, chi2_final, lambda_final;
+    int32_t iterations[8];    /* per round                                                       */
+    int32_t stop_reason[8];   /* per round: 0 iterations ran out, 1 max_trials, 2 rho == 0, 3 lambda, 4 non-finite chi2 */
+    int32_t trials, solver_failures;
+    int32_t n_inliers_pt, n_inliers_ln;
+    int32_t status;           /* PLBA_VITRACK_*                                                  */
+    int32_t reserved;
+} plba_vitrack_result;
+void plba_vitrack_default_options(plba_vitrack_options* o);
+int  plba_track_inertial(plba_problem* p, const plba_vitrack_options* opt, int B,
+                         const uint8_t* anchor_free, const double* state_i22, const double* state_j22,
+                         const double* preint142, const double* info_pvr81, const double* info_bias36,
+                         const double* prior_state22, const double* prior_info225, const double* gw3,
+                         const int32_t* pt_start, const double* Pw3, const double* uv2, const double* pt_inv_sigma2,
+                         const int32_t* ln_start, const double* sPeP6, const double* l3, const double* ln_inv_sigma2,
+                         double fx, double fy, double cx, double cy, const double* Rbc9, const double* Pbc3,
+                         uint8_t* pt_inlier, uint8_t* ln_inlier, plba_vitrack_result* out);
+
 /* ---- descriptor matching and loop-candidate checks: batched StVO::match and isLoopClosure -------------
  * plba_match_descriptors: StVO::match (stvo-pl/src/matching.cpp:41-91) for B problems in ONE launch over (problem, direction, query
  * tile), a second small launch for the tests and the counts.  Semantics, literally as coded there:

@@ -1001,6 +1001,37 @@ private:
         }
     }
 };
+// pose-only variant of the line edge against the 15-DoF state: the two rows of EdgeNavStateLine (IMU/g2otypes.h:783-825, .cpp:1306-1359) with
+// both end points held.  The reference has no such class; with it the graph of plba_track_inertial can be built from facade classes.  Its
+// position block is the true derivative under IncSmall (-l12^T Jpi Rcb), i.e. the one of fix_line_position_jacobian = 1: SURVEY B-Q1 is a
+// defect of the BA's edge and has no text to follow here.
+class EdgeNavStateLineOnlyPose : public BaseUnaryEdge<2, Vector3d, VertexNavState> {
+public:
+    EdgeNavStateLineOnlyPose() { allocJacobians({15}); }
+    void SetParams(const double& fx_, const double& fy_, const double& cx_, const double& cy_, const Matrix3d& Rbc_, const Vector3d& Pbc_, const Vector3d& sP_, const Vector3d& eP_) {
+        cam.fx = fx_; cam.fy = fy_; cam.cx = cx_; cam.cy = cy_; cam.set = true;
+        for (int i = 0; i < 3; ++i) { cam.Pbc[i] = Pbc_(i); sP[i] = sP_(i); eP[i] = eP_(i); for (int j = 0; j < 3; ++j) cam.Rbc[i * 3 + j] = Rbc_(i, j); }
+    }
+    void computeError() override { eval(false); }
+    void linearizeOplus() override { eval(true); }
+    bool isDepthPositive() { eval(false); return _depth_cache; }      // both end points
+    double chi2() const override { return chi2FromError(); }
+    CamParams cam;
+    double sP[3] = {0, 0, 0}, eP[3] = {0, 0, 0};
+private:
+    void eval(bool jac) {
+        const plba::Cam c = plba_make_cam(cam);
+        double kc[12], Jp[12], Jl[6];
+        plba::kfcam_make(c, static_cast<const VertexNavState*>(_vertices[0])->estimate().raw(), kc);
+        bool dpos = true;
+        plba::line_edge(c, kc, plba::v3(sP[0], sP[1], sP[2]), plba::v3(eP[0], eP[1], eP[2]), _measurement[0], _measurement[1], _measurement[2], true, _error.data(), Jp, Jl, dpos, jac);
+        _depth_cache = dpos;
+        if (jac) {
+            std::fill(_jac[0].begin(), _jac[0].end(), 0.0);
+            for (int r = 0; r < 2; ++r) for (int k = 0; k < 3; ++k) { J(0, 15, r, k) = Jp[r * 6 + k]; J(0, 15, r, 6 + k) = Jp[r * 6 + 3 + k]; }
+        }
+    }
+};
 
 class EdgeMarginalization : public BaseMultiEdge<-1, MarginalizationInfo> {
 public:

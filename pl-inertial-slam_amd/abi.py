@@ -128,6 +128,19 @@ class TrackResult(C.Structure):
                 ("n_inliers_pt", C.c_int32), ("n_inliers_ln", C.c_int32), ("iters", C.c_int32 * 3), ("path", C.c_int32), ("status", C.c_int32), ("good", C.c_int32)]
 
 
+class VitrackOptions(C.Structure):
+    """plba_vitrack_options of include/plba.h"""
+    _fields_ = [("rounds", C.c_int), ("iters", C.c_int), ("max_trials", C.c_int), ("robust_rounds", C.c_int), ("tau", C.c_double), ("user_lambda_init", C.c_double),
+                ("huber_pt", C.c_double), ("huber_ln", C.c_double), ("huber_imu", C.c_double), ("chi2_pt", C.c_double), ("chi2_ln", C.c_double)]
+
+
+class VitrackResult(C.Structure):
+    """plba_vitrack_result of include/plba.h"""
+    _fields_ = [("state_i22", C.c_double * 22), ("state_j22", C.c_double * 22), ("H900", C.c_double * 900), ("next_prior_info225", C.c_double * 225),
+                ("chi2_initial", C.c_double), ("chi2_final", C.c_double), ("lambda_final", C.c_double), ("iterations", C.c_int32 * 8), ("stop_reason", C.c_int32 * 8),
+                ("trials", C.c_int32), ("solver_failures", C.c_int32), ("n_inliers_pt", C.c_int32), ("n_inliers_ln", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
 class MatchOptions(C.Structure):
     """plba_match_options of include/plba.h"""
     _fields_ = [("nnr", C.c_float), ("best_lr", C.c_int)]
@@ -169,6 +182,12 @@ BOW_COMBINED, BOW_POINTS, BOW_LINES = range(3)
 RELPOSE_OK, RELPOSE_EMPTY, RELPOSE_NONFINITE, RELPOSE_RANK = range(4)
 TRACK_OK, TRACK_NONFINITE, TRACK_RANK = 0, 2, 3
 TRACK_REFINED, TRACK_ROBUST, TRACK_FEW_BEFORE, TRACK_FEW_AFTER = range(4)
+VITRACK_OK, VITRACK_NONFINITE, VITRACK_SINGULAR = 0, 2, 3
+# VitrackResult as a numpy record, for reading an array of them at once
+VITRACK_RESULT_DT = np.dtype([("state_i22", np.float64, 22), ("state_j22", np.float64, 22), ("H900", np.float64, (30, 30)), ("next_prior_info225", np.float64, (15, 15)),
+                              ("chi2_initial", np.float64), ("chi2_final", np.float64), ("lambda_final", np.float64), ("iterations", np.int32, 8), ("stop_reason", np.int32, 8),
+                              ("trials", np.int32), ("solver_failures", np.int32), ("n_inliers_pt", np.int32), ("n_inliers_ln", np.int32), ("status", np.int32), ("reserved", np.int32)])
+assert VITRACK_RESULT_DT.itemsize == C.sizeof(VitrackResult)
 REFINE_DONE, REFINE_EXHAUSTED, REFINE_NONFINITE, REFINE_FIXED, REFINE_UNSELECTED, REFINE_NO_OBS = range(6)
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
@@ -181,10 +200,12 @@ _P = C.c_void_p  # plba_problem*
 # pose graph as orc_pgo, a checker entry of its own outside this table.  refine_landmarks: g2o's structure-only solver is a stub at the
 # reference's boundary; its checker is the numpy restatement tests/refine_ref.py.  relative_pose: its checker is tests/relpose_ref.py.
 # track_pose: its checker is tests/track_ref.py.  match_descriptors, verify_loop_candidates: their checker is tests/match_ref.py.
-# bow_*: their checker is tests/bow_ref.py.  pose_graph_marginals: the reference computes none; its checker is tests/pgo_cov_ref.py)
+# bow_*: their checker is tests/bow_ref.py.  pose_graph_marginals: the reference computes none; its checker is tests/pgo_cov_ref.py.
+# track_inertial: the reference never instantiates the graph; its checker is tests/vitrack_ref.py)
 PRODUCT_ONLY = {"slide_window", "get_sizes", "marginalize_to_prior", "get_prior", "compute_marginals", "optimize_pose_graph",
                 "pose_graph_marginals",
                 "refine_default_options", "refine_landmarks", "relpose_default_options", "relative_pose", "track_default_options", "track_pose",
+                "vitrack_default_options", "track_inertial",
                 "match_default_options", "match_descriptors", "loop_default_options", "verify_loop_candidates",
                 "bow_default_options", "bow_set_vocabulary", "bow_transform", "bow_insert_keyframes", "bow_remove_keyframe", "bow_reset"}
 
@@ -246,6 +267,9 @@ SIGNATURES = {
     "track_default_options": (None, [C.POINTER(TrackOptions)]),
     "track_pose": (C.c_int, [_P, C.POINTER(TrackOptions), C.c_int, c_int32_p, c_double_p, c_double_p, c_double_p, c_int32_p, c_double_p, c_double_p,
                              c_double_p, c_double_p, C.c_double, C.c_double, C.c_double, C.c_double, c_double_p, c_uint8_p, c_uint8_p, C.POINTER(TrackResult)]),
+    "vitrack_default_options": (None, [C.POINTER(VitrackOptions)]),
+    "track_inertial": (C.c_int, [_P, C.POINTER(VitrackOptions), C.c_int, c_uint8_p] + [c_double_p] * 8 + [c_int32_p, c_double_p, c_double_p, c_double_p, c_int32_p, c_double_p,
+                                 c_double_p, c_double_p, C.c_double, C.c_double, C.c_double, C.c_double, c_double_p, c_double_p, c_uint8_p, c_uint8_p, C.POINTER(VitrackResult)]),
     "match_default_options": (None, [C.POINTER(MatchOptions)]),
     "match_descriptors": (C.c_int, [_P, C.POINTER(MatchOptions), C.c_int, c_int32_p, c_uint8_p, c_int32_p, c_uint8_p, C.POINTER(C.c_float), c_int32_p, c_int32_p,
                                     c_int32_p]),
@@ -890,6 +914,70 @@ class Problem:
             out[k] = np.array([getattr(r, k) for r in res[:B]], np.float64)
         for k in ("n_inliers_pt", "n_inliers_ln", "path", "status", "good"):
             out[k] = np.array([getattr(r, k) for r in res[:B]], np.int32)
+        out["pt_inlier"] = [pm[ps[b]:ps[b + 1]].astype(bool) for b in range(B)]
+        out["ln_inlier"] = [lm[ls[b]:ls[b + 1]].astype(bool) for b in range(B)]
+        return out
+
+    def track_inertial(self, anchor_free, state_i, state_j, preint, info_pvr, info_bias, prior_state, prior_info, gw, Pw, uv, pt_inv_sigma2, sPeP, l3,
+                       ln_inv_sigma2, cam, Rbc, Pbc, pt_inlier=None, ln_inlier=None, **opts):
+        """plba_track_inertial: B motion-only visual-inertial optimisations of two consecutive states in one launch.  anchor_free: B flags or
+        None (every anchor fixed); state_i / state_j (B, 22), preint (B, 142), info_pvr (B, 9, 9), info_bias (B, 6, 6); prior_state (B, 22) and
+        prior_info (B, 15, 15) or None when no anchor is free; gw (3,); Pw / uv / pt_inv_sigma2 / sPeP / l3 / ln_inv_sigma2: lists of B arrays
+        ((n, 3), (n, 2), (n,), (m, 6), (m, 3), (m,); an empty array or None for a problem without points or lines); cam = (fx, fy, cx, cy), Rbc
+        (3, 3), Pbc (3,); pt_inlier / ln_inlier: lists of B masks or None (all); opts: the fields of plba_vitrack_options.  Returns a dict of
+        arrays over the problems — state_i, state_j (B, 22), H (B, 30, 30), next_prior (B, 15, 15), chi2_initial, chi2_final, lambda_final,
+        iterations, stop_reason (B, 8), trials, solver_failures, n_inliers_pt, n_inliers_ln, status — and pt_inlier / ln_inlier, lists of B
+        boolean masks as the last gate left them."""
+        o = VitrackOptions()
+        self.lib.fn["vitrack_default_options"](C.byref(o))
+        for k, v in opts.items():
+            if not hasattr(o, k):
+                raise TypeError("unknown track-inertial option %r" % k)
+            setattr(o, k, v)
+        B = len(Pw)
+        if not (len(uv) == len(pt_inv_sigma2) == len(sPeP) == len(l3) == len(ln_inv_sigma2) == B):
+            raise ValueError("the feature lists must list the same problems")
+
+        def csr(lists, width):
+            arrs = [np.zeros((0, width)) if a is None else _f64(a).reshape(-1, width) for a in lists]
+            start = np.zeros(len(arrs) + 1, np.int32)
+            start[1:] = np.cumsum([len(a) for a in arrs])
+            return start, (np.concatenate(arrs) if arrs else np.zeros((0, width)))
+        ps, P = csr(Pw, 3); ps2, U2 = csr(uv, 2); ps3, WP = csr(pt_inv_sigma2, 1)
+        ls, PQ = csr(sPeP, 6); ls2, L3 = csr(l3, 3); ls3, WL = csr(ln_inv_sigma2, 1)
+        if not (np.array_equal(ps, ps2) and np.array_equal(ps, ps3) and np.array_equal(ls, ls2) and np.array_equal(ls, ls3)):
+            raise ValueError("a problem's point arrays or line arrays differ in length")
+
+        def masks(m, start):
+            if m is None:
+                return np.ones(max(int(start[-1]), 1), np.uint8)
+            if len(m) != B or any(len(np.asarray(a).ravel()) != start[b + 1] - start[b] for b, a in enumerate(m)):
+                raise ValueError("a mask list must have one entry per problem and one flag per feature")
+            flat = np.concatenate([np.asarray(a).ravel().astype(bool) for a in m]) if B else np.zeros(0, bool)
+            return np.concatenate([flat.astype(np.uint8), np.zeros(1 if flat.size == 0 else 0, np.uint8)])
+        pm, lm = masks(pt_inlier, ps), masks(ln_inlier, ls)
+
+        def rows(a, n, what):
+            if a is None:
+                return None
+            a = _f64(a).reshape(-1, n).copy()
+            if a.shape[0] != B:
+                raise ValueError("%s must have one row per problem" % what)
+            return a
+        af = None if anchor_free is None else _u8(np.asarray(anchor_free).astype(bool))
+        if af is not None and af.size != B:
+            raise ValueError("anchor_free must have one flag per problem")
+        si, sj, pre, ip, ib = rows(state_i, 22, "state_i"), rows(state_j, 22, "state_j"), rows(preint, 142, "preint"), rows(info_pvr, 81, "info_pvr"), rows(info_bias, 36, "info_bias")
+        pst, pin = rows(prior_state, 22, "prior_state"), rows(prior_info, 225, "prior_info")
+        g, R, t = _f64(gw, (3,)), _f64(Rbc, (9,)), _f64(Pbc, (3,))
+        res = (VitrackResult * max(B, 1))()
+        opt_p = lambda a: _dp(a) if len(a) else None
+        self.call("track_inertial", C.byref(o), B, _up(af), _dp(si), _dp(sj), _dp(pre), _dp(ip), _dp(ib), _dp(pst), _dp(pin), _dp(g), _ip(ps), opt_p(P), opt_p(U2),
+                  opt_p(WP), _ip(ls), opt_p(PQ), opt_p(L3), opt_p(WL), float(cam[0]), float(cam[1]), float(cam[2]), float(cam[3]), _dp(R), _dp(t), _up(pm), _up(lm), res)
+        rec = np.frombuffer(res, dtype=VITRACK_RESULT_DT, count=B)      # (one view of the B structs: H alone is 900 numbers a problem)
+        out = {k: rec[f].copy() for k, f in (("state_i", "state_i22"), ("state_j", "state_j22"), ("H", "H900"), ("next_prior", "next_prior_info225"))}
+        for k in ("chi2_initial", "chi2_final", "lambda_final", "iterations", "stop_reason", "trials", "solver_failures", "n_inliers_pt", "n_inliers_ln", "status"):
+            out[k] = rec[k].copy()
         out["pt_inlier"] = [pm[ps[b]:ps[b + 1]].astype(bool) for b in range(B)]
         out["ln_inlier"] = [lm[ls[b]:ls[b + 1]].astype(bool) for b in range(B)]
         return out
