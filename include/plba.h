@@ -974,6 +974,74 @@ int  plba_bow_insert_keyframes(plba_problem* p, const plba_bow_options* opt, int
 int  plba_bow_remove_keyframe(plba_problem* p, int kf);
 int  plba_bow_reset(plba_problem* p);
 
+/* ---- covisibility graph and loop pose graph -------------------------------------------------------------
+ * What the reference keeps as the dense counters full_graph (include/mapHandler.h; grown by expandGraphs, src/mapHandler.cpp:874-885,
+ * incremented observation by observation, :672-677, :4556-4631) is here a device-resident map of observation lists and four queries
+ * on it: the sparse rows, the dense column plba_bow_insert_keyframes takes as cov, the edge list and measurements
+ * plba_optimize_pose_graph takes, and formLocalMap's flags.  Nothing of size K^2 is formed.
+ *
+ * DEFINITION (a decision of this project).  For keyframes i != j
+ *     C[i][j] = sum over all landmarks l, points and lines together, of m_l(i) * m_l(j),
+ * m_l(k) = the number of times k occurs in l's kf_obs_list (lists are unsorted and may repeat a keyframe); C[i][i] = 0; the row and
+ * the column of a dead keyframe (live[k] == 0, the reference's map_keyframes[k] == NULL) are 0, as :3033-3038 leaves them.  On a map
+ * without removals this is the value the reference's increments maintain (tests/test_covis_cpu.py replays them).  Deviation: the
+ * reference never decrements when the BA culls an observation; the recount sees the lists as they are.
+ *
+ * plba_covis_set_map replaces the resident map: K keyframes, live (K, may be NULL: all live), and per kind a CSR over the LANDMARKS,
+ * landmark l's list being [start[l], start[l + 1]) of kf; an empty list is a removed landmark.  The device builds the
+ * keyframe -> landmark transpose itself.  info6 (may be NULL) = [K, live keyframes, landmarks, point observations, line observations,
+ * device bytes held]; plba_debug_get("covis_map") (6, at any time) returns the same, zeros without a map.  plba_covis_reset drops the
+ * map.  Re-upload to edit: there is no incremental entry.
+ *
+ * plba_covis_rows: the sparse rows of the n listed keyframes (any order, repeats allowed): entries with C >= max(1, min_count),
+ * columns ascending; row r is [row_start[r], row_start[r + 1]) of col / cnt, which hold cap entries each.  n = K with kf = 0 .. K - 1
+ * is the whole symmetric graph.  plba_covis_column: the dense full_graph[i][idx] for i < idx into cov[idx], exactly the array
+ * plba_bow_insert_keyframes takes as one keyframe's cov.
+ *
+ * plba_covis_pose_graph: the edge loop of loopClosureOptimizationCovGraphG2O (:4373-4408), literally: for i ascending and j > i
+ * ascending, both below nv <= K and both live, an edge (i, j) when C[i][j] >= min_lm_ess_graph || C[i][j] >= min_lm_cov_graph ||
+ * j - i == 1; then the n_loop loop edges (loop_ij: pairs, loop_meas12: their measurements) in the order given, which is the
+ * insertion order computeInitialGuess walks.  A dead keyframe breaks the j - i == 1 chain, as in the text: neither of its
+ * neighbours' edges to it exists and nothing bridges the gap.  meas12 of a covisibility edge = T_i^-1 T_j in pose12's layout, with
+ * T_i^-1 = [R_i^T, -R_i^T t_i] formed directly.  Deviation at rounding level: the reference's round trip through logmap_se3 /
+ * reverse_se3 / SE3Quat::exp, the identity in exact arithmetic, is not restated.  ei / ej / meas12 (edge_cap entries each) and *ne drop
+ * into plba_pose_graph without a copy.
+ *
+ * plba_covis_local_map: formLocalMap(KeyFrame*) (:955-1017).  Keyframe i is local when it is live and (i == kf || C[kf][i] >=
+ * min_lm_cov_graph || abs(kf - i) <= min_kf_local_map); a landmark is local when any keyframe of its list is.  kf_local (K), pt_local
+ * (Np), ln_local (Nl) are 0 / 1; counts3 = the local keyframes, points, lines.  Deviations: the text takes the row of the NEWEST
+ * keyframe whatever kf it was given, here the row is kf's (identical for the newest); the text dereferences removed keyframes, here a
+ * dead keyframe is never local.
+ *
+ * Contract, as the matcher's and the BoW database's: `p` supplies the device, the stream, the options and the error text; the uploaded
+ * window, prior, trace and saved state are neither read nor written; two identical sequences of calls give identical bits (all sums
+ * are integer and order-independent; meas12 is a fixed chain per entry).  Every call, plba_covis_set_map included, makes one staged
+ * copy up, one back and ONE blocking wait (plba_debug_get("host_waits")): a query counts and fills in the same stream and checks the
+ * caller's capacity on the device, so no size is read back first; the copy back is sized by cap / edge_cap.  plba_covis_reset and a
+ * refused call wait for nothing.  A capacity too small: PLBA_ERR_INVALID with the needed count in row_start[n] / *ne and nothing
+ * else written (INT32_MAX: that many or more).  Refused with PLBA_ERR_INVALID and nothing changed, outputs and resident map alike:
+ * K < 1, a negative count, starts that do not begin at 0 or descend, a keyframe index in a list outside [0, K), a total observation
+ * count that does not fit int32, a missing array with a non-zero count, a requested keyframe outside [0, K), nv outside 1 .. K, a loop
+ * index outside [0, nv) or a loop edge with i == j, a non-finite pose or loop measurement, a negative option, no options.  A query
+ * before any plba_covis_set_map: PLBA_ERR_STATE. */
+typedef struct plba_covis_options {
+    int32_t min_lm_ess_graph;   /* SlamConfig::minLMEssGraph, src/slamConfig.cpp:60                        (150) */
+    int32_t min_lm_cov_graph;   /* SlamConfig::minLMCovGraph, :61                                          (75) */
+    int32_t min_kf_local_map;   /* SlamConfig::minKFLocalMap, :62                                           (3) */
+    int32_t reserved;
+} plba_covis_options;
+void plba_covis_default_options(plba_covis_options* o);
+int  plba_covis_set_map(plba_problem* p, int K, const uint8_t* live, int Np, const int32_t* pt_start, const int32_t* pt_kf,
+                        int Nl, const int32_t* ln_start, const int32_t* ln_kf, double* info6);
+int  plba_covis_reset(plba_problem* p);
+int  plba_covis_rows(plba_problem* p, int n, const int32_t* kf, int min_count, int32_t* row_start, int cap, int32_t* col, int32_t* cnt);
+int  plba_covis_column(plba_problem* p, int idx, int32_t* cov);
+int  plba_covis_pose_graph(plba_problem* p, const plba_covis_options* opt, int nv, const double* pose12,
+                           int n_loop, const int32_t* loop_ij, const double* loop_meas12,
+                           int edge_cap, int32_t* ei, int32_t* ej, double* meas12, int* ne);
+int  plba_covis_local_map(plba_problem* p, const plba_covis_options* opt, int kf, uint8_t* kf_local, uint8_t* pt_local, uint8_t* ln_local,
+                          int32_t* counts3);
+
 /* ---- diagnostics used by the parity tests (not needed by a drop-in caller) ------------------- */
 /* Runs computeActiveErrors + buildSystem + setLambda(lambda) + Schur on the current state without
  * updating it, then exposes named internal buffers: "Hschur" (P*P row-major), "bschur" (P),
@@ -988,7 +1056,8 @@ int  plba_bow_reset(plba_problem* p);
  * "pgo_cov" (8, at any time), "pgo_cov_H" (nblk * 36 under PLBA_DIAG_PGO_COV_DUMP): the last plba_pose_graph_marginals (see there);
  * "lba_sparse" (8, at any time): the last plba_lba_visual's solver (see there);
  * "bow_db" (5, at any time): the place-recognition database, [keyframes, live keyframes, stored entries of the point vectors, of the
- * line vectors, device bytes held]. */
+ * line vectors, device bytes held];
+ * "covis_map" (6, at any time): the resident covisibility map, plba_covis_set_map's info6. */
 int plba_debug_build(plba_problem* p, double lambda, int do_solve);
 int plba_debug_get(plba_problem* p, const char* what, double* out, size_t cap, size_t* n);
 /* the same entry under its round-1 name (tests/test_gpu_parity.py); product code calls plba_dense_solve */

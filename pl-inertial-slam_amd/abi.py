@@ -178,6 +178,11 @@ class BowResult(C.Structure):
                 ("cand", C.POINTER(BowCandidate))]
 
 
+class CovisOptions(C.Structure):
+    """plba_covis_options of include/plba.h"""
+    _fields_ = [("min_lm_ess_graph", C.c_int32), ("min_lm_cov_graph", C.c_int32), ("min_kf_local_map", C.c_int32), ("reserved", C.c_int32)]
+
+
 BOW_COMBINED, BOW_POINTS, BOW_LINES = range(3)
 RELPOSE_OK, RELPOSE_EMPTY, RELPOSE_NONFINITE, RELPOSE_RANK = range(4)
 TRACK_OK, TRACK_NONFINITE, TRACK_RANK = 0, 2, 3
@@ -201,13 +206,15 @@ _P = C.c_void_p  # plba_problem*
 # reference's boundary; its checker is the numpy restatement tests/refine_ref.py.  relative_pose: its checker is tests/relpose_ref.py.
 # track_pose: its checker is tests/track_ref.py.  match_descriptors, verify_loop_candidates: their checker is tests/match_ref.py.
 # bow_*: their checker is tests/bow_ref.py.  pose_graph_marginals: the reference computes none; its checker is tests/pgo_cov_ref.py.
-# track_inertial: the reference never instantiates the graph; its checker is tests/vitrack_ref.py)
+# track_inertial: the reference never instantiates the graph; its checker is tests/vitrack_ref.py.  covis_*: their checker is
+# tests/covis_ref.py)
 PRODUCT_ONLY = {"slide_window", "get_sizes", "marginalize_to_prior", "get_prior", "compute_marginals", "optimize_pose_graph",
                 "pose_graph_marginals",
                 "refine_default_options", "refine_landmarks", "relpose_default_options", "relative_pose", "track_default_options", "track_pose",
                 "vitrack_default_options", "track_inertial",
                 "match_default_options", "match_descriptors", "loop_default_options", "verify_loop_candidates",
-                "bow_default_options", "bow_set_vocabulary", "bow_transform", "bow_insert_keyframes", "bow_remove_keyframe", "bow_reset"}
+                "bow_default_options", "bow_set_vocabulary", "bow_transform", "bow_insert_keyframes", "bow_remove_keyframe", "bow_reset",
+                "covis_default_options", "covis_set_map", "covis_reset", "covis_rows", "covis_column", "covis_pose_graph", "covis_local_map"}
 
 # name -> (restype, argtypes); every symbol plba.h declares
 SIGNATURES = {
@@ -284,6 +291,14 @@ SIGNATURES = {
                                        c_int32_p, C.POINTER(BowResult)]),
     "bow_remove_keyframe": (C.c_int, [_P, C.c_int]),
     "bow_reset": (C.c_int, [_P]),
+    "covis_default_options": (None, [C.POINTER(CovisOptions)]),
+    "covis_set_map": (C.c_int, [_P, C.c_int, c_uint8_p, C.c_int, c_int32_p, c_int32_p, C.c_int, c_int32_p, c_int32_p, c_double_p]),
+    "covis_reset": (C.c_int, [_P]),
+    "covis_rows": (C.c_int, [_P, C.c_int, c_int32_p, C.c_int, c_int32_p, C.c_int, c_int32_p, c_int32_p]),
+    "covis_column": (C.c_int, [_P, C.c_int, c_int32_p]),
+    "covis_pose_graph": (C.c_int, [_P, C.POINTER(CovisOptions), C.c_int, c_double_p, C.c_int, c_int32_p, c_double_p, C.c_int, c_int32_p, c_int32_p, c_double_p,
+                                   C.POINTER(C.c_int)]),
+    "covis_local_map": (C.c_int, [_P, C.POINTER(CovisOptions), C.c_int, c_uint8_p, c_uint8_p, c_uint8_p, c_int32_p]),
     "optimize_pose_graph": (C.c_int, [_P, C.POINTER(PoseGraph), C.c_int, C.c_double, C.c_int, C.POINTER(Stats), C.POINTER(TraceRow), C.c_int, C.POINTER(C.c_int)]),
     "pose_graph_marginals": (C.c_int, [_P, C.POINTER(PoseGraph), C.POINTER(PgoMarginals)]),
 }
@@ -1157,6 +1172,86 @@ class Problem:
 
     def bow_reset(self):
         self.call("bow_reset")
+
+    # -- covisibility graph -----------------------------------------------------------------------
+    def _covis_options(self, opts):
+        o = CovisOptions()
+        self.lib.fn["covis_default_options"](C.byref(o))
+        for k, v in opts.items():
+            if k not in ("min_lm_ess_graph", "min_lm_cov_graph", "min_kf_local_map"):
+                raise TypeError("unknown covis option %r" % k)
+            setattr(o, k, int(v))
+        return o
+
+    def covis_set_map(self, K, pt_start, pt_kf, ln_start=None, ln_kf=None, live=None):
+        """plba_covis_set_map: the landmarks' observation lists as CSR per kind (start: n + 1 entries, kf: the keyframe indices); a missing
+        kind is empty.  Returns the info array [K, live keyframes, landmarks, point observations, line observations, device bytes]."""
+        ps, pk, ls, lk = _i32(pt_start), _i32(pt_kf), _i32(ln_start), _i32(ln_kf)
+        lv = _u8(live)
+        if lv is not None and len(lv) != int(K):
+            raise ValueError("live must have K entries")
+        dims = (int(K), 0 if ps is None else len(ps) - 1, 0 if ls is None else len(ls) - 1)
+        info = np.zeros(6, np.float64)
+        self.call("covis_set_map", int(K), _up(lv), dims[1], _ip(ps), _ip(pk), dims[2], _ip(ls), _ip(lk), _dp(info))
+        self._covis_dims = dims      # (a refused call leaves the resident map, and these, as they were)
+        return info
+
+    def covis_reset(self):
+        self.call("covis_reset")
+        self._covis_dims = None
+
+    def covis_rows(self, kf, min_count=0, cap=None):
+        """plba_covis_rows: (row_start, col, cnt) of the listed keyframes' sparse rows.  cap=None: the capacity is taken from a first,
+        refused call's answer when a guess of 64 entries a row does not hold (a second device call); a given cap too small raises."""
+        kf = _i32(np.atleast_1d(kf))
+        n = len(kf)
+        rs = np.zeros(n + 1, np.int32)
+        guess = 64 * n + 64 if cap is None else int(cap)
+        for attempt in range(2):
+            col, cnt = np.zeros(max(guess, 1), np.int32), np.zeros(max(guess, 1), np.int32)
+            rc = self.lib.fn["covis_rows"](self._h, n, _ip(kf), int(min_count), _ip(rs), guess, _ip(col), _ip(cnt))
+            if rc == -1 and cap is None and attempt == 0 and guess < rs[n] < 2 ** 31 - 1:
+                guess = int(rs[n])
+                continue
+            self._ck(rc)
+            return rs, col[:rs[n]].copy(), cnt[:rs[n]].copy()
+
+    def covis_column(self, idx):
+        """plba_covis_column: full_graph[i][idx] for i < idx, the cov array of plba_bow_insert_keyframes"""
+        cov = np.zeros(max(int(idx), 1), np.int32)
+        self.call("covis_column", int(idx), _ip(cov))
+        return cov[:max(int(idx), 0)]
+
+    def covis_pose_graph(self, pose12, loop_ij=None, loop_meas12=None, edge_cap=None, **opts):
+        """plba_covis_pose_graph over the first len(pose12) keyframes: (ei, ej, meas12), the covisibility edges in the order of the
+        reference's double loop, then the loop edges; the arrays drop into Problem.pgo.  edge_cap=None: as covis_rows' cap."""
+        o = self._covis_options(opts)
+        pose = _f64(pose12, (-1, 12))
+        nv = len(pose)
+        lij = None if loop_ij is None else _i32(loop_ij).reshape(-1, 2)
+        lm = None if loop_meas12 is None else _f64(loop_meas12, (-1, 12))
+        nl = 0 if lij is None else len(lij)
+        if nl and (lm is None or len(lm) != nl):
+            raise ValueError("loop_meas12 must have one row per loop edge")
+        guess = 8 * nv + nl + 64 if edge_cap is None else int(edge_cap)
+        ne = C.c_int(0)
+        for attempt in range(2):
+            ei, ej, z = np.zeros(max(guess, 1), np.int32), np.zeros(max(guess, 1), np.int32), np.zeros((max(guess, 1), 12), np.float64)
+            rc = self.lib.fn["covis_pose_graph"](self._h, C.byref(o), nv, _dp(pose), nl, _ip(lij), _dp(lm), guess, _ip(ei), _ip(ej), _dp(z), C.byref(ne))
+            if rc == -1 and edge_cap is None and attempt == 0 and guess < ne.value < 2 ** 31 - 1:
+                guess = ne.value
+                continue
+            self._ck(rc)
+            return ei[:ne.value].copy(), ej[:ne.value].copy(), z[:ne.value].copy()
+
+    def covis_local_map(self, kf, **opts):
+        """plba_covis_local_map: dict of kf_local (K), pt_local (Np), ln_local (Nl) as uint8 flags and counts (3)"""
+        o = self._covis_options(opts)
+        K, Np, Nl = self._covis_dims if getattr(self, "_covis_dims", None) else (int(self.debug_get("covis_map")[0]), 0, 0)
+        fk, fp, fl = np.zeros(max(K, 1), np.uint8), np.zeros(max(Np, 1), np.uint8), np.zeros(max(Nl, 1), np.uint8)
+        c3 = np.zeros(3, np.int32)
+        self.call("covis_local_map", C.byref(o), int(kf), _up(fk), _up(fp), _up(fl), _ip(c3))
+        return dict(kf_local=fk[:K], pt_local=fp[:Np], ln_local=fl[:Nl], counts=c3)
 
     def preintegrate(self, sample_start, t, gyr, acc, t_prev, t_curr, bg, ba, gyr_meas_cov, acc_meas_cov):
         """KeyFrame::ComputeIMUPreIntSinceLastFrame for M intervals (plba_preintegrate); time stamps as np.longdouble."""

@@ -44,6 +44,7 @@ static const size_t PARK_MAX = 2;
 static void reset_for_reuse(plba_problem* p, const plba_options* opt) {
     marg_discard(p);      // (plba_destroy has done so already)
     plba_bow_discard(p);
+    plba_covis_discard(p);
     if (opt) p->opt = *opt; else plba_default_options(&p->opt);
     p->err[0] = 0;
     p->stream = p->ctx.stream; p->own_stream = true;
@@ -195,6 +196,7 @@ void plba_destroy(plba_problem* p) {
     marg_discard(p);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     plba_bow_discard(p);
+    plba_covis_discard(p);
     if (p->have_ctx) {
         (void)hipStreamSynchronize(p->ctx.stream);
         std::lock_guard<std::mutex> g(g_ctx_mu);
@@ -2715,6 +2717,13 @@ int plba_debug_get(plba_problem* p, const char* what, double* out, size_t cap, s
         plba_bow_describe(p, d5);
         if (n) *n = 5;
         for (size_t i = 0; out && i < cap && i < 5; ++i) out[i] = d5[i];
+        return PLBA_OK;
+    }
+    if (w == "covis_map") {    // (host-side record of the resident covisibility map)
+        double d6[6];
+        plba_covis_describe(p, d6);
+        if (n) *n = 6;
+        for (size_t i = 0; out && i < cap && i < 6; ++i) out[i] = d6[i];
         return PLBA_OK;
     }
     if (p->dirty) FAIL(p, PLBA_ERR_STATE, "debug_get before debug_build/optimize");

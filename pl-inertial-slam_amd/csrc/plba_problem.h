@@ -222,6 +222,7 @@ struct DenseWork {
 
 struct MargPending;      // a plba_marginalize_to_prior still in the stream (plba_marg.hip)
 struct BowState;         // the vocabularies and the keyframe database of place recognition (plba_bow.hip)
+struct CovisState;       // the resident observation lists of the covisibility graph (plba_covis.hip)
 // host image of the fused landmark-major passes' group structure (build_lm_groups, plba_api.hip); kept with the cached context
 // (HostCtx) so that its tables are not re-allocated (and their pages not re-faulted) by every BA call
 struct LmHost {
@@ -321,6 +322,7 @@ struct plba_problem {
     double pgo_cov[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // last plba_pose_graph_marginals (plba_debug_get "pgo_cov", include/plba.h)
     std::vector<double> pgo_cov_H;                     // options.diag & PLBA_DIAG_PGO_COV_DUMP: the device's Hblk (nblk x 36) of that call (plba_debug_get "pgo_cov_H")
     plba::BowState* bow = nullptr;       // place recognition (plba_bow_*): made by the first plba_bow_set_vocabulary, dropped by plba_bow_discard()
+    plba::CovisState* covis = nullptr;   // covisibility graph (plba_covis_*): made by plba_covis_set_map, dropped by plba_covis_discard()
     long host_waits = 0;                  // times the library blocked the calling thread on the device (plba_debug_get "host_waits")
     plba::Robust rob;
     // shard
@@ -490,6 +492,9 @@ inline hipError_t plba_h2d(plba_problem* p, void* dst_dev, const void* src, size
 // plba_bow.hip: frees the vocabularies and the database (the owner has synchronised the stream); plba_debug_get("bow_db")
 void plba_bow_discard(plba_problem* p);
 void plba_bow_describe(const plba_problem* p, double out5[5]);
+// plba_covis.hip: frees the resident map (the owner has synchronised the stream); plba_debug_get("covis_map")
+void plba_covis_discard(plba_problem* p);
+void plba_covis_describe(const plba_problem* p, double out6[6]);
 
 #define PLBA_FAIL(p, code, ...)                             \
     do {                                                    \
