@@ -25,6 +25,11 @@ level 1, the point and line Huber kernels off — and reach what only the levels
   behind                           level 0 everywhere; three points, the first end of a line, the second of another and both of a third behind a camera
   stage2_mixed, stage2_cross9      state and levels of the quad oracle's own optimize(5) + gate_outliers(5.991), carried by the fixture
 
+One case reaches what only the vertex ids reach:
+  biasfirst                        mixed with the two vertex ids of every odd keyframe exchanged: there vid_bias < vid_pvr and the bias block
+                                   comes first in the pose layout, on the even keyframes the PVR block does (tests/step_exact.py: the offsets
+                                   from which the state is updated)
+
 A case is dict(make, opts, wide, lambdas):
   make(window_module, carried) -> the window (`carried`: what the fixture carries for the case — the prior of prior13, the state and
   levels of the stage2 cases —, None elsewhere).  Besides what upload_window reads a window may hold po_level / lo_level (uint8 per
@@ -176,6 +181,16 @@ def _noimu_lostkf(W, carried):
     return w
 
 
+def _biasfirst(W, carried):
+    w = CASES["mixed"]["make"](W, None)
+    k = w["kf"] = dict(w["kf"])
+    vp, vb = np.asarray(k["vid_pvr"]).copy(), np.asarray(k["vid_bias"]).copy()
+    assert (vb > vp).all() and (np.diff(vp) > 0).all()
+    odd = np.arange(len(vp)) % 2 == 1
+    k["vid_pvr"], k["vid_bias"] = np.where(odd, vb, vp).astype(vp.dtype), np.where(odd, vp, vb).astype(vb.dtype)
+    return w
+
+
 def camera_of(w, k):
     """(R, C) of keyframe k's camera at the window's estimate: Pc = R (Pw - C) (Pc = Rcb Rwb^T (Pw - Pwb) - Rcb Pbc)"""
     x, y, z, s = w["kf"]["q"][k]
@@ -284,6 +299,7 @@ CASES.update({
     "behind": _case(_behind),
     "stage2_mixed": _case(_stage2("mixed")),
     "stage2_cross9": _case(_stage2("cross9")),
+    "biasfirst": _case(_biasfirst),
 })
 NEEDS_PRIOR = ("prior13",)      # the prior is data the fixture carries (the reference's marginalization of the window's own first BA)
 NEEDS_STATE = {"stage2_mixed": "mixed", "stage2_cross9": "cross9"}      # state and levels the fixture carries (stage1_state of the named window)
@@ -295,7 +311,8 @@ NEEDS_STATE = {"stage2_mixed": "mixed", "stage2_cross9": "cross9"}      # state 
 # These two lose lambda = 0.05 altogether.  (tests/test_build_exact_cpu.py recomputes every dropped pair's noise and asserts that it is over its cap.)  On two more only the first trial's chi2 is over its cap while the system and x are within:
 #   points_only 0.05   chi2_trial 1 389 847 u (32 x = 4.9e-9)
 #   noimu7 0.05        chi2_trial 5 336 431 u (32 x = 1.9e-8)
-# there the built system and x are held and the trial is not compared.
+# there the built system and x are held and the trial is not compared.  biasfirst is mixed under other vertex ids and goes the same way:
+#   biasfirst 0.05     x_pose 916 047 u, x_lm 311 473 u, chi2_trial 1 008 315 u
 # The gated cases (caps: 112 590 u on a quantity of the system, 281 475 u on x and chi2_trial), each judged before any device ran:
 #   gated_mixed 0.05       x_pose 2 097 882 u, x_lm 1 790 251 u, chi2_trial 9 722 725 u      (Hschur 34 300 u, within)
 #   gated_short2 0.05      x_pose 758 434 u, x_lm 296 635 u, chi2_trial 382 507 u
@@ -308,7 +325,7 @@ NEEDS_STATE = {"stage2_mixed": "mixed", "stage2_cross9": "cross9"}      # state 
 # (`behind` keeps the protocol's own first lambda only: a landmark 0.3 m from a camera has Jacobians a hundred times those of the rest of
 # the window and the solve loses the digits; its built system — the rows with z < 0 — is held there.)  The trial alone:
 #   levels_robust_on 0.05  chi2_trial 559 790 u                                             (x_pose 207 137 u, x_lm 209 660 u, within)
-DROPPED = {("mixed", 0.05), ("lines_only", 0.05),
+DROPPED = {("mixed", 0.05), ("lines_only", 0.05), ("biasfirst", 0.05),
            ("gated_mixed", 0.05), ("gated_short2", 0.05), ("gated_steps3", 0.05), ("noimu_lostkf", 0.05), ("behind", 5.0), ("behind", 0.05),
            ("stage2_mixed", 0.05), ("stage2_cross9", 0.05)}
 TRIAL_DROPPED = {("points_only", 0.05), ("noimu7", 0.05), ("levels_robust_on", 0.05)}
